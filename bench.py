@@ -23,9 +23,18 @@ cells k % N == r -- each y keeps the same share of its column as in the full
 Gram (about (j+1)/N pairs), so a step has the full Gram's composition.  Other
 kernels: cell k is in slice k % S and rank r computes slice (t*N + r).  Per-GPU
 work is fixed, so scaling is weak; the ranks all-gather the step's Gram
-entries with the engine's own RCCL communicator (sk_comm_allgather).  --full
-times one call of the product path itself: sk_gram_sharded over all N ranks
-(cells, all-gather, host assembly of the whole mirrored matrix).
+entries with the engine's own RCCL communicator (sk_comm_allgather).
+--whole-gram times one call of the product path itself: sk_gram_sharded over
+all N ranks (cells, all-gather, host assembly of the whole mirrored matrix).
+
+A plain run sets up, warms up, times the steps and prints the result line (the
+roofline in it is arithmetic on the timed launches' own HIP-event timings and
+the committed traffic profile: no run of its own).  --full adds what takes
+work of its own after the timed steps: the CPU baseline (the C oracle on a
+sample of the same Gram's pairs) and the parity check of the benched kernel
+classes against those oracle values.  --dump-outputs DIR writes what the last
+timed step delivered (dump_outputs); the inputs are seeded, so two builds run
+with the same arguments can be compared output for output.
 
 Other SURVEY.md §8 configurations (--config): c2 ss_kernel 256 x L150,
 c3 4-D stem kernel 1024 x L200, c4 BPLA 2048 alignments L~200, c5 DAG stem
@@ -71,7 +80,7 @@ CONFIGS = {
     # pairs/s against 218.4k / 218.3k with 1/16 on one box (r06u; r05w: 1/16
     # 206.2k, 1/24 203.7k, 1/48 201.2k -- the class launches' fill and last
     # round over more pairs); the whole Gram in one call (sk_gram_sharded,
-    # bench --full) 220.0k (r06s); 8 divides the driver's 1, 2, 4 and 8 GPUs
+    # bench --whole-gram) 220.0k (r06s); 8 divides the driver's 1, 2, 4 and 8 GPUs
     # (asynchronous calls, below: +0.7 %, r06q)
     "ns": dict(kernel="ss", cls="LSuStemStrKernel", n=4096, L=200, slices=8, cid=2, cpu_pairs=12288,
                async_calls=True),
@@ -104,17 +113,23 @@ CONFIGS = {
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default 5; --whole-gram: 1)")
+    ap.add_argument("--warmup", type=int, default=None, help="untimed steps first (default 1; --whole-gram: 0)")
     ap.add_argument("--config", default="ns", choices=sorted(CONFIGS))
     ap.add_argument("--n", type=int, default=None, help="number of examples")
     ap.add_argument("--length", type=int, default=None)
     ap.add_argument("--slices", type=int, default=None)
-    ap.add_argument("--full", action="store_true", help="time every slice (whole Gram)")
+    ap.add_argument("--whole-gram", action="store_true",
+                    help="a step is the whole Gram through the product path (sk_gram_sharded)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the CPU baseline (C oracle sample) and the parity "
+                         "check against it")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's outputs to DIR/<name>.npy")
     ap.add_argument("--sync", action="store_true", help="synchronous compute calls for every config")
     ap.add_argument("--async", dest="async_calls", action="store_true",
                     help="asynchronous compute calls (sk_set_async) for every config (default: C4 only)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--cpu-pairs", type=int, default=None, help="pairs in the CPU sample")
     ap.add_argument("--pmc-json", default=None, help="traffic profile (default profiles/<kind>_traffic.json)")
     ap.add_argument("--cpu-stub", default=None, metavar="MODULE:FUNC",
@@ -580,9 +595,15 @@ class GpuEngine:
         self.ctx.allgather(self.out.data_ptr(), self.per, self.gathered.data_ptr())
         return tm
 
-    def full(self):
-        self.ctx.gram_sharded(self.ds, self.kern, normalize=False)
+    def whole_gram(self):
+        self.gram = self.ctx.gram_sharded(self.ds, self.kern, normalize=False)
         return None if self.async_on else dict(self.ctx.last_timing(), **self.ctx.last_launch_ms())
+
+    def outputs(self, sizes):
+        """The last step's Gram entries as its caller receives them: every
+        rank's slice of the all-gathered buffer, without the padding."""
+        g = self.gathered.cpu().numpy()
+        return np.concatenate([g[r * self.per: r * self.per + c] for r, c in enumerate(sizes)])
 
     def totals(self):
         """Summed timings of the calls since the last totals() (async mode;
@@ -665,8 +686,11 @@ class CpuStubEngine(GpuEngine):
                 raise AssertionError(f"cpu stub: rank {r}'s gathered slice differs")
             self.checked += rx.size
 
-    def full(self):
-        raise SystemExit("--full is the GPU product path (sk_gram_sharded)")
+    def whole_gram(self):
+        raise SystemExit("--whole-gram is the GPU product path (sk_gram_sharded)")
+
+    def outputs(self, sizes):
+        return np.concatenate([self.last[r][:c].numpy() for r, c in enumerate(sizes)])
 
     def sync(self):
         pass
@@ -726,6 +750,26 @@ def make_plan(kind, n, world, rank, S):
     return slice_of, max(per, 1), desc, iu.size
 
 
+# ------------------------------------------------------------------ outputs
+DUMP_MAX_BYTES = 60_000_000  # under the 64 MB a dump may take, headers included
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: DIR/<name>.npy (float64) of what the last timed step
+    delivered -- `gram_entries`, the step's all-gathered Gram cells in rank
+    order, or `gram`, the whole matrix of a --whole-gram step.  At most 64 MB
+    in all: a larger array is written as a fixed, seeded sample of its
+    flattened entries (ascending index)."""
+    os.makedirs(path, exist_ok=True)
+    budget = DUMP_MAX_BYTES // max(1, len(arrays))
+    for name, arr in arrays.items():
+        arr = np.ascontiguousarray(arr, dtype=np.float64).ravel()
+        if arr.nbytes > budget:
+            keep = np.random.default_rng(0x5EED0D01).choice(arr.size, size=budget // 8, replace=False)
+            arr = arr[np.sort(keep)]
+        np.save(os.path.join(path, name + ".npy"), arr)
+
+
 # ------------------------------------------------------------------ main
 def main():
     a = parse()
@@ -745,8 +789,12 @@ def main():
     shapes = np.array([eng.ds.shape(i) for i in range(a.n)], dtype=np.float64)
 
     S = a.slices
-    if a.full:
-        a.steps, a.warmup = 1, 0
+    if a.steps is None:
+        a.steps = 1 if a.whole_gram else 5
+    if a.warmup is None:
+        a.warmup = 0 if a.whole_gram else 1
+    if a.steps < 1 or a.warmup < 0:
+        raise SystemExit("--steps must be at least 1 and --warmup at least 0")
     # the configured step size whatever --steps is: past S / N steps the slices
     # repeat (each step recomputed in full, as C2's whole-Gram steps repeat),
     # rather than shrinking the step to (warmup + steps) * N slices
@@ -755,16 +803,16 @@ def main():
     eng.alloc(per)
 
     def run_step(step):
-        if a.full:  # the product path: sk_gram_sharded over all ranks
+        if a.whole_gram:  # the product path: sk_gram_sharded over all ranks
             from stem_kernel_amd import shard
-            tm = eng.full()
+            tm = eng.whole_gram()
             x, y = shard.rank_pairs(a.n, world, rank)
             return x, y, tm
         x, y = slice_of(step)
         return x, y, eng.step(x, y)
 
     # the steps' cell lists are host bookkeeping: formed before the timed region
-    if not a.full:
+    if not a.whole_gram:
         for t in range(a.warmup + a.steps):
             slice_of(t)
         if a.cpu_stub:
@@ -814,6 +862,13 @@ def main():
     if a.cpu_stub:
         last = a.warmup + a.steps - 1
         eng.verify(lambda r: slice_of(last, r))
+    if a.dump_outputs and rank == 0:
+        if a.whole_gram:
+            dump_outputs(a.dump_outputs, {"gram": eng.gram})
+        else:
+            last = a.warmup + a.steps - 1
+            sizes = [slice_of(last, r)[0].size for r in range(world)]
+            dump_outputs(a.dump_outputs, {"gram_entries": eng.outputs(sizes)})
 
     if rank == 0:
         value = total_pairs / elapsed
@@ -835,7 +890,7 @@ def main():
                             "sk_stem4d_pre_kernel" if os.environ.get("SK4_SPAN") else "sk_stem4d_col_kernel",
                             "bpla": "sk_bpla_fast_kernel"}[kind]
         cpu, parity = None, None
-        if not a.no_cpu_baseline and world == 1 and not a.cpu_stub:  # rank 0 at N=1 only
+        if a.full and not a.no_cpu_baseline and world == 1 and not a.cpu_stub:  # rank 0 at N=1 only
             cpu, cpairs, cvals, ccomp = cpu_baseline(cfg, eng.data, a.cpu_pairs)
             # the baseline's oracle values double as a parity check of the
             # benched kernel classes on the same inputs (1e-6 relative): the
@@ -892,7 +947,7 @@ def main():
                              "c3": "stem_kernel (4-D) default -p BPMatrix full_dp",
                              "c4": "bpla_kernel default"}[a.config],
                 "parallelism": f"cyclic cell plan x{world} (sk_comm_allgather, RCCL)"
-                               + (" -- full Gram via sk_gram_sharded" if a.full else ""),
+                               + (" -- full Gram via sk_gram_sharded" if a.whole_gram else ""),
                 "mean_nodes": float(shapes[:, 0].mean()), "mean_edges": float(shapes[:, 1].mean()),
                 "mean_bpfreq": float(shapes[:, 2].mean()),
                 "host_build_s": round(eng.t_build, 2), "upload_s": round(eng.t_upload, 3),

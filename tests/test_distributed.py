@@ -59,14 +59,27 @@ def test_assemble_matches_reference_normalisation():
 
 
 def test_assemble_n8192_under_a_second():
+    """The bound is on what the assembly costs, not on what else the host is
+    doing: the best of three calls (a single call on a shared or freshly
+    started host also pays for its neighbours and for the first touch of the
+    library and the thread pool), and the CPUs this process may run on rather
+    than the machine's."""
     import time
     n, world = 8192, 8
     per = shard.max_pairs(n, world)
     parts = [np.ones(per) for _ in range(world)]
-    t = time.perf_counter()
-    out = shard.assemble(parts, n, world, normalize=True)
-    assert time.perf_counter() - t < 1.0 * max(1, 8 // (os.cpu_count() or 8))
-    assert out[0, 1] == 1.0
+    try:
+        cpus = len(os.sched_getaffinity(0))
+    except AttributeError:
+        cpus = os.cpu_count() or 8
+    best = float("inf")
+    for _ in range(3):
+        t = time.perf_counter()
+        out = shard.assemble(parts, n, world, normalize=True)
+        best = min(best, time.perf_counter() - t)
+        assert out[0, 1] == 1.0
+        del out
+    assert best < 1.0 * max(1, 8 // cpus)
 
 
 def _free_port():
@@ -276,6 +289,25 @@ def test_bench_spawns_its_own_ranks(config, n, length):
     assert line["n_gpus"] == 2 and line["steps"] == 2
     assert line["stub_checked_pairs"] > 0
     assert line["value"] > 0 and line["roofline"] is None
+
+
+def test_bench_dumps_the_last_timed_steps_outputs(tmp_path):
+    """`--dump-outputs DIR` writes the last timed step's gathered Gram cells
+    as float64 (here step 3 of the plan: cells k % 8 == 3 of the seeded NS
+    set, the stub's values), and a plain run times exactly --steps steps and
+    leaves the CPU baseline and the parity check to --full."""
+    import stem_kernel_amd as ska
+    from tests import bench_stub
+    line = _bench(["--gpus", "1", "--config", "ns", "--n", "10", "--length", "40", "--steps", "3",
+                   "--warmup", "1", "--cpu-stub", "tests.bench_stub:compute", "--dump-outputs", str(tmp_path)])
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0
+    assert line["cpu_baseline"] is None and line["parity"] is None
+    assert sorted(os.listdir(tmp_path)) == ["gram_entries.npy"]
+    got = np.load(tmp_path / "gram_entries.npy")
+    iu, ju = np.triu_indices(10)
+    seqs = ska.random_sequences(10, 40, 0x5EED0002)
+    ref = bench_stub.compute(seqs, ska.LSuStemStrKernel().params, iu[3::8], ju[3::8])
+    assert got.dtype == np.float64 and np.array_equal(got, ref)
 
 
 def test_bench_rank_failure_stops_the_job():

@@ -11,5 +11,5 @@ for r in 1 2; do
   timeout -k 10 300 python3 -u bench.py --config c3 --no-cpu-baseline > $OUT/c3_new_$r.log 2>&1 || { tail -20 $OUT/c3_new_$r.log; exit 1; }
   line $OUT/c3_new_$r.log "c3 gsum r$r"
 done
-timeout -k 10 300 python3 -u bench.py --config c3 > $OUT/c3_cpu.log 2>&1 || { tail -20 $OUT/c3_cpu.log; exit 1; }
+timeout -k 10 300 python3 -u bench.py --full --config c3 > $OUT/c3_cpu.log 2>&1 || { tail -20 $OUT/c3_cpu.log; exit 1; }
 line $OUT/c3_cpu.log "c3 gsum with cpu baseline/parity"

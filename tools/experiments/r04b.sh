@@ -8,9 +8,9 @@ run() {  # name, env, args
   timeout -k 10 400 env "$@" > $OUT/$name.log 2>&1 || { tail -20 $OUT/$name.log; exit 1; }
   line $OUT/$name.log "$name"
 }
-run c3_col python3 -u bench.py --config c3
+run c3_col python3 -u bench.py --full --config c3
 run c3_pre SK4_NO_COL=1 python3 -u bench.py --config c3 --no-cpu-baseline
-run ns_async python3 -u bench.py --config ns
+run ns_async python3 -u bench.py --full --config ns
 run ns_sync python3 -u bench.py --config ns --no-cpu-baseline --sync
 run ns_w12 SK_LIB_PATH=$PWD/build/libsk_w12.so python3 -u bench.py --config ns --no-cpu-baseline
 run ns_w12n SK_LIB_PATH=$PWD/build/libsk_w12n.so python3 -u bench.py --config ns --no-cpu-baseline

@@ -11,7 +11,7 @@ run() {
 }
 timeout -k 10 300 python -u -m pytest tests/test_stem4d.py -m gpu -x -q --timeout 200 --timeout-method thread > $OUT/pt4d.log 2>&1 || { tail -20 $OUT/pt4d.log; exit 1; }
 tail -1 $OUT/pt4d.log
-run c3_col python3 -u bench.py --config c3
+run c3_col python3 -u bench.py --full --config c3
 run c4_async python3 -u bench.py --config c4 --no-cpu-baseline
 run c4_sync python3 -u bench.py --config c4 --no-cpu-baseline --sync
 for r in 1 2; do

@@ -16,4 +16,4 @@ run c3_col python3 -u bench.py --config c3 --no-cpu-baseline
 run c3_pf1 SK_LIB_PATH=$PWD/build/libsk_c3pf1.so python3 -u bench.py --config c3 --no-cpu-baseline
 run c3_w16 SK_LIB_PATH=$PWD/build/libsk_c3w16.so python3 -u bench.py --config c3 --no-cpu-baseline
 run c3_pre SK4_NO_COL=1 python3 -u bench.py --config c3 --no-cpu-baseline
-run ns python3 -u bench.py --config ns
+run ns python3 -u bench.py --full --config ns

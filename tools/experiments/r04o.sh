@@ -11,7 +11,7 @@ run() {
 }
 SK_LIB_PATH=$PWD/build/libsk_r3.so timeout -k 10 400 python -u -m pytest tests/test_bpla.py tests/test_async.py tests/test_large_configs.py -m gpu -x -q --timeout 120 --timeout-method thread > $OUT/pytest_r3.log 2>&1 || { tail -30 $OUT/pytest_r3.log; exit 1; }
 tail -1 $OUT/pytest_r3.log
-run r3_1 SK_LIB_PATH=$PWD/build/libsk_r3.so python3 -u bench.py --config c4
+run r3_1 SK_LIB_PATH=$PWD/build/libsk_r3.so python3 -u bench.py --full --config c4
 run base_1 python3 -u bench.py --config c4 --no-cpu-baseline
 run r3_2 SK_LIB_PATH=$PWD/build/libsk_r3.so python3 -u bench.py --config c4 --no-cpu-baseline
 run base_2 python3 -u bench.py --config c4 --no-cpu-baseline

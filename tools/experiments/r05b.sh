@@ -14,4 +14,4 @@ timeout -k 10 400 python3 -u -m pytest -x -v --timeout 240 --timeout-method thre
 tail -3 $OUT/pytest.log
 run c3_col512 python3 -u bench.py --config c3 --no-cpu-baseline --slices 1025 --steps 3 --warmup 1
 run c3_col512_w6 SK4C_W=6 python3 -u bench.py --config c3 --no-cpu-baseline --slices 1025 --steps 3 --warmup 1
-run c3_col768 python3 -u bench.py --config c3 --slices 684 --steps 2 --warmup 1 --cpu-pairs 8
+run c3_col768 python3 -u bench.py --full --config c3 --slices 684 --steps 2 --warmup 1 --cpu-pairs 8

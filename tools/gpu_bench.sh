@@ -28,5 +28,5 @@ cp $OUT/${KIND}_traffic.json profiles/${KIND}_traffic.json
 tail -2 $OUT/traffic.log
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $ROOT/$OUT/prof -o run --output-format csv -- \
   python3 $ROOT/bench.py --config $CFG --no-cpu-baseline > $OUT/bench_prof.log 2>&1 || { tail -20 $OUT/bench_prof.log; exit 1; }
-timeout -k 10 400 python3 bench.py --config $CFG > $OUT/bench.log 2>&1 || { tail -20 $OUT/bench.log; exit 1; }
+timeout -k 10 400 python3 bench.py --full --config $CFG > $OUT/bench.log 2>&1 || { tail -20 $OUT/bench.log; exit 1; }
 tail -1 $OUT/bench.log

@@ -8,5 +8,5 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout
 tail -1 $OUT/pytest_gpu.log
 timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1 || { tail -20 $OUT/smoke.log; exit 1; }
 tail -1 $OUT/smoke.log
-timeout -k 10 500 python3 -u bench.py --config $CFG > $OUT/bench_$CFG.log 2>&1 || { tail -20 $OUT/bench_$CFG.log; exit 1; }
+timeout -k 10 500 python3 -u bench.py --full --config $CFG > $OUT/bench_$CFG.log 2>&1 || { tail -20 $OUT/bench_$CFG.log; exit 1; }
 tail -1 $OUT/bench_$CFG.log | cut -c1-400

@@ -12,7 +12,7 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout
 tail -1 $OUT/pytest_gpu.log
 timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1 || { tail -20 $OUT/smoke.log; exit 1; }
 tail -1 $OUT/smoke.log
-run ns SK_HOST_STATS=1 python3 -u bench.py --config ns
+run ns SK_HOST_STATS=1 python3 -u bench.py --full --config ns
 grep "\[sk" $OUT/ns.log | head -12
 run c4 python3 -u bench.py --config c4 --no-cpu-baseline
 run c3 python3 -u bench.py --config c3 --no-cpu-baseline

@@ -38,5 +38,5 @@ run_pmc LDS SQ_LDS_IDX_ACTIVE SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_INSTS_VALU SQ
 python3 tools/profile_summary.py $OUT $CFG $KSUB $OUT/${CFG}_traffic.json > $OUT/summary.log 2>&1 || { tail -20 $OUT/summary.log; exit 1; }
 cp $OUT/${CFG}_traffic.json profiles/${CFG}_traffic.json
 find $OUT/prof -name "*kernel_stats.csv" -exec cp {} $OUT/kernel_stats.csv \;
-timeout -k 10 500 python3 -u bench.py --config $CFG > $OUT/bench.log 2>&1 || { tail -20 $OUT/bench.log; exit 1; }
+timeout -k 10 500 python3 -u bench.py --full --config $CFG > $OUT/bench.log 2>&1 || { tail -20 $OUT/bench.log; exit 1; }
 tail -1 $OUT/bench.log | cut -c1-300

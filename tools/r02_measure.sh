@@ -15,7 +15,7 @@ for c in ns c4; do
   db=$(find $OUT/prof_$c -name "*.db" -print -quit)
   python3 tools/rocpd_stats.py $db $OUT/${c}_kernel_stats.csv && head -4 $OUT/${c}_kernel_stats.csv | cut -c1-120
   tail -1 $OUT/prof_$c.log > $OUT/prof_${c}_line.json
-  timeout -k 10 500 python3 -u bench.py --config $c > $OUT/bench_$c.log 2>&1 || { tail -20 $OUT/bench_$c.log; exit 1; }
+  timeout -k 10 500 python3 -u bench.py --full --config $c > $OUT/bench_$c.log 2>&1 || { tail -20 $OUT/bench_$c.log; exit 1; }
   tail -1 $OUT/bench_$c.log | cut -c1-200
 done
 timeout -s KILL 200 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_SALU SQ_WAVES SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR -d $ROOT/$OUT/pmc_c4 -o run --output-format csv -- python3 $ROOT/bench.py --config c4 --steps 1 --warmup 0 --no-cpu-baseline > $OUT/pmc_c4.log 2>&1 || { tail -20 $OUT/pmc_c4.log; exit 1; }
