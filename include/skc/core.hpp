@@ -155,7 +155,10 @@ class Engine {
   // The engine's GPU McCaskill fold of gap-erased rows (BPMatrix FOLD without
   // ViennaRNA).  Prints a one-line notice the first time: values built from
   // it are not comparable with the reference's ViennaRNA-based outputs.
-  void fold(const std::vector<std::string>& rows, int flags, std::vector<std::vector<double>>& out) {
+  // n_samples > 0: BPMatrix SFOLD, the pair frequencies of that many sampled
+  // structures per row (sk_fold_sample), reproducible from seed.
+  void fold(const std::vector<std::string>& rows, int flags, std::vector<std::vector<double>>& out,
+            uint32_t n_samples = 0, uint64_t seed = 0) {
     std::vector<const char*> p;
     size_t total = 0;
     for (const std::string& s : rows) {
@@ -174,7 +177,12 @@ class Engine {
                      "for that)\n");
         fold_notice_ = true;
       }
-      check(sk_fold_mccaskill(ctx_, (int32_t)p.size(), p.data(), flags, all.data(), nullptr), ctx_);
+      if (n_samples > 0)
+        check(sk_fold_sample(ctx_, (int32_t)p.size(), p.data(), flags, (int32_t)n_samples, seed, all.data(),
+                             nullptr, nullptr),
+              ctx_);
+      else
+        check(sk_fold_mccaskill(ctx_, (int32_t)p.size(), p.data(), flags, all.data(), nullptr), ctx_);
     }
     out.clear();
     size_t o = 0;
@@ -454,7 +462,8 @@ struct BPMatrixOptions {
   // common/bpmatrix.h:17-38 (+ the fold hook)
   bool alifold = false, contrafold = false, no_GU = false, no_closingGU = false,
        no_LonelyPairs = false;
-  uint n_samples = 0;
+  uint n_samples = 0;          // > 0: SFOLD, stochastic sampling (common/bpmatrix.cpp:179-232)
+  uint64_t sampling_seed = 0;  // the engine's own: the reference seeds from the clock
   bool use_pf_scale_mfe = false;
   FoldFn fold;  // empty: the engine's GPU McCaskill
 };
@@ -474,12 +483,13 @@ inline void fold_rows(RowsData& d, const BPMatrixOptions& opts) {
     }
     return;
   }
-  if (opts.alifold || opts.contrafold || opts.n_samples > 0)
-    throw "only the FOLD method (McCaskill per row) is supported by the engine";
+  if (opts.alifold || opts.contrafold)
+    throw "only the FOLD and SFOLD methods (McCaskill or sampled structures per row) are supported by the engine";
+  if (opts.n_samples > 0x7fffffffu) throw "--sampling: too many samples";
   Engine::get().fold(erased,
                      (opts.no_GU ? SK_FOLD_NO_GU : 0) | (opts.no_closingGU ? SK_FOLD_NO_CLOSING_GU : 0) |
                          (opts.no_LonelyPairs ? SK_FOLD_NO_LONELY_PAIRS : 0),
-                     d.bpp);
+                     d.bpp, opts.n_samples, opts.sampling_seed);
 }
 
 inline void add_rows(sk_dataset* ds, const std::string& label, const RowsData& d, float th) {

@@ -322,6 +322,26 @@ int sk_fold_synthetic(const char *seq, int32_t n, int32_t no_gu, double *out);
 #define SK_FOLD_NO_LONELY_PAIRS 4
 int sk_fold_mccaskill(sk_context *ctx, int32_t n, const char *const *seqs, int32_t flags,
                       double *out, double *log_z);
+/* Stochastic structure sampling on the GPU (csrc/kernels/fold_sample.hip):
+ * BPMatrix SFOLD, common/bpmatrix.cpp:179-232 (--sampling N: pf_fold, N x
+ * pbacktrack, bpp(i,j) = the fraction of samples holding the pair).  After
+ * the inside pass of sk_fold_mccaskill's kernel, n_samples structures per
+ * sequence are drawn from the Boltzmann ensemble of the same loop model:
+ * P(structure) = exp(-E/kT) / Z.  seqs, flags and the length limit are those
+ * of sk_fold_mccaskill.  out_bpp (optional): the layout of sk_fold_mccaskill's
+ * out, count / n_samples in double.  out_structs (optional): for each k in
+ * order, n_samples rows of n_k chars '(' ')' '.', no terminators.  log_z
+ * (optional): ln Z per sequence.  At least one of out_bpp and out_structs.
+ * Where the reference seeds ViennaRNA's generator from the clock, the result
+ * here is a function of the arguments alone: sample s of sequence k is drawn
+ * from a counter-based generator keyed by (seed, k, s, decision number), so
+ * it does not depend on n_samples or on how the call is batched. */
+int sk_fold_sample(sk_context *ctx, int32_t n, const char *const *seqs, int32_t flags,
+                   int32_t n_samples, uint64_t seed, double *out_bpp, char *out_structs,
+                   double *log_z);
+/* The sampler's generator on the host: the uniform double in [0, 1) of draw
+ * number draw of sample `sample` of sequence `seq` under seed. */
+double sk_fold_sample_uniform(uint64_t seed, int32_t seq, int32_t sample, int32_t draw);
 /* n examples of n_rows equal-length rows (rows[i*n_rows + r]), built on
  * n_threads host threads (0 = hardware concurrency) from the caller's
  * per-row bpp (bpp_rows[i*n_rows + r], layout of sk_dataset_add; ignored
@@ -337,6 +357,11 @@ int sk_dataset_add_batch(sk_dataset *ds, int32_t n, int32_t n_rows, const char *
 int sk_dataset_add_folded(sk_context *ctx, sk_dataset *ds, int32_t n, int32_t n_rows,
                           const char *const *rows, const char *const *labels, float th,
                           int32_t fold_flags, int32_t n_threads);
+/* sk_dataset_add_folded with sk_fold_sample's bpp (BPMatrix SFOLD); the
+ * generator's sequence index is the row's index i*n_rows + r in the call. */
+int sk_dataset_add_sampled(sk_context *ctx, sk_dataset *ds, int32_t n, int32_t n_rows,
+                           const char *const *rows, const char *const *labels, float th,
+                           int32_t fold_flags, int32_t n_samples, uint64_t seed, int32_t n_threads);
 
 /* BPLA gradients, the bpla_optimizer's per-pair step: for k < n_pairs,
  * value[k] = BPLAKernel::compute_gradients(xs[x[k]], ys[y[k]], score_table,

@@ -44,7 +44,11 @@
 //     each gap-erased, lowercased row with it (honouring --noGU and
 //     --noClosingGU, --noLonelyPairs; --use-alifold is refused) and
 //     averages alignment rows as the reference does
-//     (common/bpmatrix.cpp:306-342).  BPMatrix::Options::fold plugs in any
+//     (common/bpmatrix.cpp:306-342).  Options::n_samples > 0 (SFOLD,
+//     --sampling N, common/bpmatrix.cpp:179-232) gives the pair frequencies
+//     of that many structures sampled on the GPU (sk_fold_sample),
+//     reproducible from Options::sampling_seed where the reference seeds
+//     from the clock.  BPMatrix::Options::fold plugs in any
 //     other folder (e.g. ViennaRNA itself, or skc::synthetic_fold);
 //   - elapsed times are wall-clock seconds (the reference sums boost::timer
 //     CPU seconds);

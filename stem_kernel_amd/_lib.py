@@ -87,6 +87,12 @@ SIGNATURES = {
                                    C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "sk_fold_synthetic": (C.c_int, [C.c_char_p, C.c_int32, C.c_int32, _F64P]),
     "sk_fold_mccaskill": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_char_p), C.c_int32, _F64P, _F64P]),
+    "sk_fold_sample": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_char_p), C.c_int32, C.c_int32, C.c_uint64,
+                                 _F64P, C.c_void_p, _F64P]),
+    "sk_fold_sample_uniform": (C.c_double, [C.c_uint64, C.c_int32, C.c_int32, C.c_int32]),
+    "sk_dataset_add_sampled": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.POINTER(C.c_char_p),
+                                         C.POINTER(C.c_char_p), C.c_float, C.c_int32, C.c_int32,
+                                         C.c_uint64, C.c_int32]),
     "sk_dataset_add_batch": (C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(C.c_char_p),
                                        C.POINTER(_F64P), C.POINTER(C.c_char_p), C.c_float,
                                        C.c_int32, C.c_int32]),

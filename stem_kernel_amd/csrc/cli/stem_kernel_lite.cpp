@@ -17,7 +17,9 @@
 //
 // Differences, by necessity: base-pairing probabilities come from the
 // engine's GPU McCaskill (sk_fold_mccaskill) instead of ViennaRNA;
-// --use-alifold is refused; .bz2 output goes through the
+// --sampling N (BPMatrix SFOLD) draws its structures on the GPU
+// (sk_fold_sample) from --sampling-seed, the engine's own option, instead of
+// the clock; --use-alifold is refused; .bz2 output goes through the
 // system's libbz2.so.1 (loaded at run time: the image has the library but not
 // its headers).  The
 // reference's default kernel (SuStemStr without --log) only estimates memory
@@ -39,6 +41,7 @@
 #include <iostream>
 #include <map>
 #include <sstream>
+#include <stdexcept>
 #include <string>
 #include <vector>
 
@@ -100,7 +103,10 @@ const char* kUsage =
     "  --noClosingGU               disallow closing GU base-pairs\n"
     "  --noLonelyPairs             disallow lonely base-pairs\n"
     "  --use-alifold               use pf_alifold (not supported by the engine)\n"
-    "  --pf-scale                  calculate appropriciate pf_scales using MFE (no effect)\n";
+    "  --pf-scale                  calculate appropriciate pf_scales using MFE (no effect)\n"
+    "  --sampling arg (=0)         use stochastic sampling for producing base pairing probability\n"
+    "                              matrices\n"
+    "  --sampling-seed arg (=0)    seed of the sampled structures (reproducible, not the clock)\n";
 
 // boost::program_options-like parsing with allow_unregistered(): known
 // options are consumed (long "--name value" / "--name=value", short "-x
@@ -114,6 +120,19 @@ bool parse(int argc, char** argv, Options& o, std::vector<std::string>& extra, b
     std::function<void(const std::string&)> set;
   };
   auto to_f = [](const std::string& v) { return std::stod(v); };
+  // whole-string unsigned values ("12x" and "-1" are invalid, as for boost's uint)
+  auto to_u64 = [](const std::string& v) {
+    size_t used = 0;
+    if (v.empty() || !std::isdigit((unsigned char)v[0])) throw std::invalid_argument(v);
+    const unsigned long long x = std::stoull(v, &used);
+    if (used != v.size()) throw std::invalid_argument(v);
+    return (uint64_t)x;
+  };
+  auto to_uint = [&](const std::string& v) {
+    const uint64_t x = to_u64(v);
+    if (x > 0x7fffffffull) throw std::out_of_range(v);
+    return (unsigned)x;
+  };
   std::vector<Opt> opts = {
       {"help", 'h', false, [&](const std::string&) { help = true; }},
       {"threads", 't', true, [&](const std::string& v) { o.n_th = (unsigned)std::stoul(v); }},
@@ -140,6 +159,8 @@ bool parse(int argc, char** argv, Options& o, std::vector<std::string>& extra, b
       {"noLonelyPairs", 0, false, [&](const std::string&) { o.bp.no_LonelyPairs = true; }},
       {"use-alifold", 0, false, [&](const std::string&) { o.bp.alifold = true; }},
       {"pf-scale", 0, false, [&](const std::string&) { o.bp.use_pf_scale_mfe = true; }},
+      {"sampling", 0, true, [&](const std::string& v) { o.bp.n_samples = to_uint(v); }},
+      {"sampling-seed", 0, true, [&](const std::string& v) { o.bp.sampling_seed = to_u64(v); }},
   };
   for (int k = 1; k < argc; ++k) {
     const std::string a = argv[k];

@@ -21,34 +21,10 @@
 // n up to ~1,400; P(i,j) = Qb Hb / Z is scale-free.
 #include <hip/hip_runtime.h>
 
+#include "fold_dev.h"
 #include "launch.h"
 
 namespace sk {
-
-// pair type of codes (a, b), a * 4 + b -> 4 bits of a 64-bit constant (no
-// memory access: a __constant__ table indexed per thread is a vector load):
-// {0,0,0,5, 0,0,1,0, 0,2,0,4, 6,0,3,0}  CG1 GC2 GU3 UG4 AU5 UA6
-constexpr uint64_t kFoldPairBits = 0x306402001005000ull;
-
-struct FoldTables {  // views into P.tab (FoldLaunch::tab layout)
-  const double *st, *hp, *bu, *in, *ni, *au, *scp;
-  double mlc, mli;
-};
-
-__device__ __forceinline__ int pair_raw(int a, int b) {
-  return (a < 0 || b < 0) ? 0 : (int)((kFoldPairBits >> (4 * (a * 4 + b))) & 0xfu);
-}
-__device__ __forceinline__ bool is_gu(int t) { return t == 3 || t == 4; }
-
-// interior / bulge / stack loop factor (unscaled), t1 = type(i,j), t2 = type(q,p)
-__device__ __forceinline__ double fold_interior(const FoldTables& T, int t1, int t2, int n1, int n2,
-                                                bool ncg) {
-  const int n = n1 + n2;
-  if (n == 0) return T.st[t1 * 7 + t2];
-  if (ncg && (is_gu(t1) || is_gu(t2))) return 0.0;
-  if (n1 == 0 || n2 == 0) return n == 1 ? T.bu[1] * T.st[t1 * 7 + t2] : T.bu[n] * T.au[t1] * T.au[t2];
-  return T.in[n] * T.ni[abs(n1 - n2)] * T.au[t1] * T.au[t2];
-}
 
 // block-wide sum (at most 8 waves), result in every thread
 __device__ __forceinline__ double block_sum(double v, double* red) {
@@ -125,11 +101,7 @@ __global__ void __launch_bounds__(512) sk_fold_kernel(FoldLaunch P) {
   const double* scp = T.scp;
   const bool ngu = P.no_gu != 0, ncg = P.no_closing_gu != 0;
   const uint8_t* __restrict__ lp = P.lp ? P.lp + sq.lp_off : nullptr;
-  auto ptype = [&](int i, int j) {
-    const int t = pair_raw(c[i], c[j]);
-    if (lp && !lp[(size_t)i * n + j]) return 0;  // --noLonelyPairs (host table)
-    return (ngu && is_gu(t)) ? 0 : t;
-  };
+  auto ptype = [&](int i, int j) { return fold_ptype(c, lp, n, ngu, i, j); };
   auto D = [&](int d, int i) { return (size_t)d * n + i; };
   // ring slot of diagonal d, and the slot of d - 1 / d + 1 given d's
   auto slot = [](int d) { return d % kFoldRing; };
@@ -223,6 +195,8 @@ __global__ void __launch_bounds__(512) sk_fold_kernel(FoldLaunch P) {
   }
   const double Z = Q5[n];
   if (tid == 0 && P.log_z) P.log_z[blockIdx.x] = log(Z) - (double)n * P.log_sc;
+  // the structure sampler (fold_sample.hip) walks Qb, Qm, Qm1 and Q5 only
+  if (P.inside_only) return;
   if (tid == 0) H5[n] = 1.0;
   __syncthreads();
   for (int k = n - 1; k >= 0; --k) {

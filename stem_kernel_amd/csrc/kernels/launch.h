@@ -297,6 +297,7 @@ struct FoldLaunch {
   double* work = nullptr;           // per sequence 6 n^2 + 2 (n + 1) doubles (fold_work_doubles)
   double* out = nullptr;
   double* log_z = nullptr;        // per sequence of the launch (nullptr: not wanted)
+  int32_t inside_only = 0;        // stop after the inside pass and Q5 (the sampler's input)
 };
 // the fold kernel keeps the interior-loop window of the inside / outside
 // tables in LDS for sequences up to this length (33 n doubles)
@@ -310,6 +311,24 @@ bool fold_gtab(const FoldLaunch& P, int max_n);
 size_t fold_lds_bytes(const FoldLaunch& P, int max_n);
 inline size_t fold_work_doubles(size_t n) { return 6 * n * n + 2 * (n + 1); }
 hipError_t launch_fold(const FoldLaunch& P, int n_seqs, int max_n, hipStream_t st);
+
+// Stochastic structure sampling (fold_sample.hip): walks the inside tables an
+// inside_only fold launch left in F.work, one wavefront per structure.
+struct FoldSampleLaunch {
+  FoldLaunch F;                 // the fold launch whose tables are walked (seqs, codes, tab, lp, work)
+  uint32_t* cnt = nullptr;      // per sequence at FoldSeq::out_off: packed pair counts (zeroed by the host)
+  char* structs = nullptr;      // optional: per sequence at n_samples * seq_off, n_samples rows of n chars
+                                // (filled with '.' by the host)
+  int32_t* status = nullptr;    // one word, 0 = ok (kFoldSample* below)
+  int32_t n_samples = 0;
+  int32_t seq_base = 0;         // index of the launch's first sequence in the whole call (generator key)
+  uint64_t seed = 0;
+};
+constexpr int32_t kFoldSampleRunaway = 1;   // more than 2 n + 2 decisions in one sample
+constexpr int32_t kFoldSampleNoWeight = 2;  // a decision's candidates sum to 0 or a non-finite value
+constexpr int32_t kFoldSampleStack = 3;     // more open segments than n / 2 + 4
+size_t fold_sample_lds_bytes(const FoldLaunch& P, int max_n);
+hipError_t launch_fold_sample(const FoldSampleLaunch& P, int n_seqs, int max_n, hipStream_t st);
 
 enum CombineMode : int32_t {
   kCombineStem = 0,      // K = stem

@@ -28,6 +28,7 @@
 
 #include "../../include/stem_kernel.h"
 #include "host/fold_params.h"
+#include "kernels/fold_rng.h"
 #include "host/sk_internal.h"
 #include "kernels/device_set.h"
 #include "kernels/launch.h"
@@ -4128,12 +4129,23 @@ void lonely_pair_table(const int8_t* c, int n, bool no_gu, uint8_t* lp) {
     }
 }
 
-int sk_fold_mccaskill(sk_context* ctx, int32_t n, const char* const* seqs, int32_t flags,
-                      double* out, double* log_z) {
-  if (!ctx || n < 0 || (n > 0 && (!seqs || !out))) return fail(ctx, SK_ERR_INVALID, "null argument");
-  if (flags & ~(SK_FOLD_NO_GU | SK_FOLD_NO_CLOSING_GU | SK_FOLD_NO_LONELY_PAIRS))
-    return fail(ctx, SK_ERR_UNSUPPORTED, "fold: unknown flag");
+namespace {
+// what sk_fold_sample adds to a fold call: after the inside pass of each
+// batch, n_samples structures per sequence are drawn on the same stream
+struct FoldSampling {
+  int32_t n_samples = 0;
+  uint64_t seed = 0;
+  char* structs = nullptr;  // optional, sk_fold_sample's out_structs
+};
+
+// sk_fold_mccaskill (sm == nullptr: out gets the McCaskill probabilities) and
+// sk_fold_sample (out, optional, gets count / n_samples): the batches, their
+// buffers and the fold launch are the same
+int fold_run(sk_context* ctx, int32_t n, const char* const* seqs, int32_t flags, double* out,
+             double* log_z, const FoldSampling* sm) {
   const bool no_lp = (flags & SK_FOLD_NO_LONELY_PAIRS) != 0;
+  const size_t ns = sm ? (size_t)sm->n_samples : 0;
+  const bool want_str = sm && sm->structs;
   if (n == 0) return SK_OK;
   std::vector<int> len(n);
   int max_len = 0;
@@ -4151,6 +4163,7 @@ int sk_fold_mccaskill(sk_context* ctx, int32_t n, const char* const* seqs, int32
   const double budget = std::min(16e9, 0.4 * (double)free_b);
   hipStream_t S = ctx->stream;
   size_t out_host = 0;  // packed output offset of sequence k (host)
+  size_t str_host = 0;  // sampled structures written so far (host)
   for (int32_t b0 = 0; b0 < n;) {
     // batch: sequences whose tables fit the budget (at least one)
     std::vector<sk::FoldSeq> sq;
@@ -4162,7 +4175,9 @@ int sk_fold_mccaskill(sk_context* ctx, int32_t n, const char* const* seqs, int32
     for (; b1 < n; ++b1) {
       const size_t nn = (size_t)len[b1];
       const size_t w = sk::fold_work_doubles(nn);
-      if (!sq.empty() && (double)(work + w) * 8.0 > budget) break;
+      // (the sampled structures of the batch count too: n_samples chars per nucleotide)
+      const double strb = want_str ? (double)(codes.size() + nn) * (double)ns : 0.0;
+      if (!sq.empty() && (double)(work + w) * 8.0 + strb > budget) break;
       sk::FoldSeq f;
       f.seq_off = (int64_t)codes.size();
       f.work_off = (int64_t)work;
@@ -4183,8 +4198,11 @@ int sk_fold_mccaskill(sk_context* ctx, int32_t n, const char* const* seqs, int32
     fold_tables(bmax, L, tab);  // sized by this batch's longest sequence
     if (sk::fold_lds_bytes(L, bmax) > sk::kFoldLdsMax)
       return fail(ctx, SK_ERR_UNSUPPORTED, "fold: sequence too long for the fold kernel's LDS");
+    if (sm && sk::fold_sample_lds_bytes(L, bmax) > sk::kFoldLdsMax)
+      return fail(ctx, SK_ERR_UNSUPPORTED, "fold: sequence too long for the sampling kernel's LDS");
+    const size_t strn = want_str ? codes.size() * ns : 0;  // sampled structures, chars
     size_t need = sq.size() * sizeof(sk::FoldSeq) + codes.size() + lp.size() + tab.size() * 8 +
-                  (outn + nb) * 8 + 7 * 256;
+                  (outn + nb) * 8 + strn + 10 * 256;
     int rc = ensure_work(ctx, need);
     if (rc) return rc;
     rc = ensure_scratch(ctx, std::max<size_t>(work * 8, 64));
@@ -4205,6 +4223,12 @@ int sk_fold_mccaskill(sk_context* ctx, int32_t n, const char* const* seqs, int32
     SK_HIP(ctx, hipMemcpyAsync(d_tab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, S));
     SK_HIP(ctx, hipMemsetAsync(ctx->scratch, 0, work * 8, S));
     SK_HIP(ctx, hipMemsetAsync(d_out, 0, std::max<size_t>(outn, 1) * 8, S));
+    // sampling: d_out holds the uint32 pair counts (zeroed above)
+    char* d_str = want_str ? A.take<char>(std::max<size_t>(strn, 1)) : nullptr;
+    int32_t* d_status = sm ? A.take<int32_t>(1) : nullptr;
+    if (want_str && strn) SK_HIP(ctx, hipMemsetAsync(d_str, '.', strn, S));
+    if (sm) SK_HIP(ctx, hipMemsetAsync(d_status, 0, sizeof(int32_t), S));
+    L.inside_only = sm ? 1 : 0;
     L.seqs = d_sq;
     L.codes = d_codes;
     L.tab = d_tab;
@@ -4213,7 +4237,27 @@ int sk_fold_mccaskill(sk_context* ctx, int32_t n, const char* const* seqs, int32
     L.log_z = d_lz;
     SK_HIP(ctx, sk::launch_fold(L, nb, bmax, S));
     std::vector<double> lz(nb);
-    if (outn) SK_HIP(ctx, hipMemcpyAsync(out + out_host, d_out, outn * 8, hipMemcpyDeviceToHost, S));
+    std::vector<uint32_t> cnt;
+    int32_t status = 0;
+    if (sm) {
+      sk::FoldSampleLaunch SL;
+      SL.F = L;
+      SL.cnt = reinterpret_cast<uint32_t*>(d_out);
+      SL.structs = d_str;
+      SL.status = d_status;
+      SL.n_samples = sm->n_samples;
+      SL.seq_base = b0;
+      SL.seed = sm->seed;
+      SK_HIP(ctx, sk::launch_fold_sample(SL, nb, bmax, S));
+      if (out && outn) {
+        cnt.resize(outn);
+        SK_HIP(ctx, hipMemcpyAsync(cnt.data(), d_out, outn * 4, hipMemcpyDeviceToHost, S));
+      }
+      if (strn) SK_HIP(ctx, hipMemcpyAsync(sm->structs + str_host, d_str, strn, hipMemcpyDeviceToHost, S));
+      SK_HIP(ctx, hipMemcpyAsync(&status, d_status, sizeof(int32_t), hipMemcpyDeviceToHost, S));
+    } else if (outn) {
+      SK_HIP(ctx, hipMemcpyAsync(out + out_host, d_out, outn * 8, hipMemcpyDeviceToHost, S));
+    }
     SK_HIP(ctx, hipMemcpyAsync(lz.data(), d_lz, nb * 8, hipMemcpyDeviceToHost, S));
     SK_HIP(ctx, hipStreamSynchronize(S));
     for (int k = 0; k < nb; ++k) {
@@ -4221,10 +4265,45 @@ int sk_fold_mccaskill(sk_context* ctx, int32_t n, const char* const* seqs, int32
         return fail(ctx, SK_ERR_UNSUPPORTED, "fold: partition function out of double range (sequence too long)");
       if (log_z) log_z[b0 + k] = lz[k];
     }
+    if (status == sk::kFoldSampleRunaway)
+      return fail(ctx, SK_ERR_HIP, "fold sampling: a walk made more than 2 n + 2 decisions");
+    if (status == sk::kFoldSampleNoWeight)
+      return fail(ctx, SK_ERR_HIP, "fold sampling: a decision's candidates sum to 0 or a non-finite value");
+    if (status != 0) return fail(ctx, SK_ERR_HIP, "fold sampling: more open segments than the stack holds");
+    // bpp = count / n_samples (common/bpmatrix.cpp:220-226)
+    for (size_t a = 0; a < cnt.size(); ++a) out[out_host + a] = (double)cnt[a] / (double)ns;
     out_host += outn;
+    str_host += strn;
     b0 = b1;
   }
   return SK_OK;
+}
+}  // namespace
+
+int sk_fold_mccaskill(sk_context* ctx, int32_t n, const char* const* seqs, int32_t flags,
+                      double* out, double* log_z) {
+  if (!ctx || n < 0 || (n > 0 && (!seqs || !out))) return fail(ctx, SK_ERR_INVALID, "null argument");
+  if (flags & ~(SK_FOLD_NO_GU | SK_FOLD_NO_CLOSING_GU | SK_FOLD_NO_LONELY_PAIRS))
+    return fail(ctx, SK_ERR_UNSUPPORTED, "fold: unknown flag");
+  return fold_run(ctx, n, seqs, flags, out, log_z, nullptr);
+}
+
+int sk_fold_sample(sk_context* ctx, int32_t n, const char* const* seqs, int32_t flags,
+                   int32_t n_samples, uint64_t seed, double* out_bpp, char* out_structs, double* log_z) {
+  if (!ctx || n < 0 || (n > 0 && !seqs)) return fail(ctx, SK_ERR_INVALID, "null argument");
+  if (n_samples < 1) return fail(ctx, SK_ERR_INVALID, "fold sampling: n_samples must be at least 1");
+  if (!out_bpp && !out_structs) return fail(ctx, SK_ERR_INVALID, "fold sampling: no output asked for");
+  if (flags & ~(SK_FOLD_NO_GU | SK_FOLD_NO_CLOSING_GU | SK_FOLD_NO_LONELY_PAIRS))
+    return fail(ctx, SK_ERR_UNSUPPORTED, "fold: unknown flag");
+  FoldSampling sm;
+  sm.n_samples = n_samples;
+  sm.seed = seed;
+  sm.structs = out_structs;
+  return fold_run(ctx, n, seqs, flags, out_bpp, log_z, &sm);
+}
+
+double sk_fold_sample_uniform(uint64_t seed, int32_t seq, int32_t sample, int32_t draw) {
+  return sk::rng_uniform(sk::rng_stream(seed, seq, sample), draw);
 }
 
 namespace {
@@ -4273,9 +4352,11 @@ int sk_dataset_add_batch(sk_dataset* ds, int32_t n, int32_t n_rows, const char* 
   return add_examples_threaded(ds, n, n_rows, rows, bpp_rows, labels, th, use_bp, n_threads);
 }
 
-int sk_dataset_add_folded(sk_context* ctx, sk_dataset* ds, int32_t n, int32_t n_rows,
-                          const char* const* rows, const char* const* labels, float th,
-                          int32_t fold_flags, int32_t n_threads) {
+namespace {
+// sk_dataset_add_folded (n_samples = 0) and sk_dataset_add_sampled
+int add_folded(sk_context* ctx, sk_dataset* ds, int32_t n, int32_t n_rows, const char* const* rows,
+               const char* const* labels, float th, int32_t fold_flags, int32_t n_samples, uint64_t seed,
+               int32_t n_threads) {
   if (!ctx || !ds || n < 0 || n_rows < 1 || (n > 0 && !rows)) return fail(ctx, SK_ERR_INVALID, "null argument");
   if (ds->uploaded) return fail(ctx, SK_ERR_INVALID, "dataset already uploaded");
   const size_t nr = (size_t)n * n_rows;
@@ -4292,12 +4373,28 @@ int sk_dataset_add_folded(sk_context* ctx, sk_dataset* ds, int32_t n, int32_t n_
     off[r + 1] = off[r] + (m > 1 ? m * (m - 1) / 2 : 0);
   }
   std::vector<double> bpp(std::max<size_t>(off[nr], 1));
-  int rc = sk_fold_mccaskill(ctx, (int32_t)nr, eptr.data(), fold_flags, bpp.data(), nullptr);
+  int rc = n_samples > 0 ? sk_fold_sample(ctx, (int32_t)nr, eptr.data(), fold_flags, n_samples, seed, bpp.data(),
+                                          nullptr, nullptr)
+                         : sk_fold_mccaskill(ctx, (int32_t)nr, eptr.data(), fold_flags, bpp.data(), nullptr);
   if (rc) return rc;
   std::vector<const double*> bptr(nr);
   for (size_t r = 0; r < nr; ++r) bptr[r] = bpp.data() + off[r];
   rc = add_examples_threaded(ds, n, n_rows, rows, bptr.data(), labels, th, 1, n_threads);
   return rc ? fail(ctx, rc, "example build failed") : SK_OK;
+}
+}  // namespace
+
+int sk_dataset_add_folded(sk_context* ctx, sk_dataset* ds, int32_t n, int32_t n_rows,
+                          const char* const* rows, const char* const* labels, float th,
+                          int32_t fold_flags, int32_t n_threads) {
+  return add_folded(ctx, ds, n, n_rows, rows, labels, th, fold_flags, 0, 0, n_threads);
+}
+
+int sk_dataset_add_sampled(sk_context* ctx, sk_dataset* ds, int32_t n, int32_t n_rows,
+                           const char* const* rows, const char* const* labels, float th,
+                           int32_t fold_flags, int32_t n_samples, uint64_t seed, int32_t n_threads) {
+  if (n_samples < 1) return fail(ctx, SK_ERR_INVALID, "fold sampling: n_samples must be at least 1");
+  return add_folded(ctx, ds, n, n_rows, rows, labels, th, fold_flags, n_samples, seed, n_threads);
 }
 
 int sk_random_sequences(uint64_t* state, int32_t n_seqs, int32_t len, char* out) {

@@ -348,11 +348,15 @@ class Dataset:
 
     @classmethod
     def folded(cls, ctx: "Context", alns, labels=None, th: float = 0.01, no_gu: bool = False,
-               no_closing_gu: bool = False, threads: int = 0, no_lonely_pairs: bool = False):
+               no_closing_gu: bool = False, threads: int = 0, no_lonely_pairs: bool = False,
+               n_samples: int = 0, seed: int = 0):
         """Examples whose rows are folded on ctx's GPU (sk_fold_mccaskill, the
         engine's McCaskill in place of Vienna pf_fold) and built on host
         threads (sk_dataset_add_folded).  ``alns``: sequences or alignments
-        of equal row count."""
+        of equal row count.  ``n_samples`` > 0: the bpp are the pair
+        frequencies of that many sampled structures per row
+        (sk_dataset_add_sampled, the reference's --sampling), reproducible
+        from ``seed``."""
         alns = [[a] if isinstance(a, str) else list(a) for a in alns]
         ds = cls()
         n = len(alns)
@@ -363,8 +367,14 @@ class Dataset:
         rarr = (C.c_char_p * max(len(flat), 1))(*flat)
         larr = None if labels is None else (C.c_char_p * n)(*[l.encode() for l in labels])
         flags = (1 if no_gu else 0) | (2 if no_closing_gu else 0) | (4 if no_lonely_pairs else 0)
-        ctx._chk(lib().sk_dataset_add_folded(ctx.handle, ds._h, n, nr, rarr, larr, C.c_float(th),
-                                             flags, threads))
+        if n_samples < 0:
+            raise ValueError("n_samples must not be negative")
+        if n_samples > 0:
+            ctx._chk(lib().sk_dataset_add_sampled(ctx.handle, ds._h, n, nr, rarr, larr, C.c_float(th),
+                                                  flags, n_samples, seed, threads))
+        else:
+            ctx._chk(lib().sk_dataset_add_folded(ctx.handle, ds._h, n, nr, rarr, larr, C.c_float(th),
+                                                 flags, threads))
         return ds
 
     def __len__(self):
@@ -495,6 +505,45 @@ class Context:
             res.append(out[o:o + z].copy())
             o += z
         return (res, lz[:n]) if log_z else res
+
+    def fold_sample(self, seqs: Sequence[str], n_samples: int, seed: int = 0, no_gu: bool = False,
+                    no_closing_gu: bool = False, no_lonely_pairs: bool = False,
+                    structures: bool = False, log_z: bool = False):
+        """Pair frequencies of ``n_samples`` structures per sequence drawn from
+        the Boltzmann ensemble on this GPU (sk_fold_sample, the reference's
+        --sampling): a list of packed upper triangles, count / n_samples.
+        With ``structures`` also, per sequence, the list of the sampled
+        dot-bracket strings; with ``log_z`` also ln Z per sequence (in that
+        order).  Sample s of sequence k depends on (seed, k, s) only."""
+        seqs = list(seqs)
+        n = len(seqs)
+        sizes = [len(s) * (len(s) - 1) // 2 for s in seqs]
+        out = np.zeros(max(sum(sizes), 1))
+        lz = np.zeros(max(n, 1))
+        sarr = (C.c_char_p * max(n, 1))(*[s.encode() for s in seqs])
+        flags = (1 if no_gu else 0) | (2 if no_closing_gu else 0) | (4 if no_lonely_pairs else 0)
+        sbuf = None
+        if structures:
+            sbuf = np.zeros(max(sum(len(s) for s in seqs) * max(n_samples, 0), 1), np.uint8)
+        self._chk(lib().sk_fold_sample(self._h, n, sarr, flags, n_samples, seed,
+                                       out.ctypes.data_as(C.POINTER(C.c_double)),
+                                       sbuf.ctypes.data if structures else None,
+                                       lz.ctypes.data_as(C.POINTER(C.c_double))))
+        res, o = [], 0
+        for z in sizes:
+            res.append(out[o:o + z].copy())
+            o += z
+        ret = [res]
+        if structures:
+            raw, strs, o = sbuf.tobytes(), [], 0
+            for s in seqs:
+                m = len(s)
+                strs.append([raw[o + k * m:o + (k + 1) * m].decode("ascii") for k in range(n_samples)])
+                o += m * n_samples
+            ret.append(strs)
+        if log_z:
+            ret.append(lz[:n])
+        return ret[0] if len(ret) == 1 else tuple(ret)
 
     def upload(self, ds: Dataset):
         self._chk(lib().sk_dataset_upload(self._h, ds.handle))
