@@ -169,14 +169,7 @@ class Engine {
     {
       std::lock_guard<std::mutex> g(mu_);
       open_locked();
-      if (!fold_notice_ && !std::getenv("SK_QUIET_FOLD")) {
-        std::fprintf(stderr,
-                     "stem_kernel_amd: base-pairing probabilities from the engine's McCaskill fold "
-                     "(Turner-1999 core loop model, not ViennaRNA): kernel values are not comparable "
-                     "with ViennaRNA-based reference outputs (pass bpp through BPMatrix::Options::fold "
-                     "for that)\n");
-        fold_notice_ = true;
-      }
+      notice_locked();
       if (n_samples > 0)
         check(sk_fold_sample(ctx_, (int32_t)p.size(), p.data(), flags, (int32_t)n_samples, seed, all.data(),
                              nullptr, nullptr),
@@ -194,11 +187,34 @@ class Engine {
     }
   }
 
+  // The engine's consensus fold of one alignment (sk_fold_alignment, BPMatrix
+  // ALIFOLD without ViennaRNA): ONE matrix over the alignment's columns.
+  void fold_alignment(const std::vector<std::string>& rows, int flags, std::vector<double>& out) {
+    std::vector<const char*> p;
+    for (const std::string& s : rows) p.push_back(s.c_str());
+    const size_t m = rows.empty() ? 0 : rows[0].size();
+    out.assign(std::max<size_t>(m > 1 ? m * (m - 1) / 2 : 0, 1), 0.0);
+    const int32_t nr = (int32_t)rows.size();
+    std::lock_guard<std::mutex> g(mu_);
+    open_locked();
+    notice_locked();
+    check(sk_fold_alignment(ctx_, 1, &nr, p.data(), flags, out.data(), nullptr), ctx_);
+  }
+
  private:
   struct Entry {
     DsPtr ds;
     uint64_t used;
   };
+  void notice_locked() {
+    if (fold_notice_ || std::getenv("SK_QUIET_FOLD")) return;
+    std::fprintf(stderr,
+                 "stem_kernel_amd: base-pairing probabilities from the engine's McCaskill fold "
+                 "(Turner-1999 core loop model, not ViennaRNA): kernel values are not comparable "
+                 "with ViennaRNA-based reference outputs (pass bpp through BPMatrix::Options::fold "
+                 "for that)\n");
+    fold_notice_ = true;
+  }
   static DsPtr make_ds() {
     sk_dataset* raw = nullptr;
     check(sk_dataset_create(&raw));
@@ -453,6 +469,7 @@ struct RowsData {
   std::vector<std::vector<double>> bpp;  // per row, gap-erased
   float th = 0.0f;
   bool use_bp = false;
+  bool consensus = false;  // bpp holds ONE matrix over the alignment's columns (consensus fold)
 };
 
 // BPMatrix(list<string>, pf_scale, opts) (common/bpmatrix.cpp:122-128,
@@ -464,6 +481,11 @@ struct BPMatrixOptions {
        no_LonelyPairs = false;
   uint n_samples = 0;          // > 0: SFOLD, stochastic sampling (common/bpmatrix.cpp:179-232)
   uint64_t sampling_seed = 0;  // the engine's own: the reference seeds from the clock
+  // the engine's own: one consensus fold per alignment (sk_fold_alignment) in
+  // place of the averaged per-row folds; n_samples > 0 wins, as SFOLD does in
+  // the reference's Options::method().  (alifold, the reference's spelling,
+  // stays refused.)
+  bool consensus = false;
   bool use_pf_scale_mfe = false;
   FoldFn fold;  // empty: the engine's GPU McCaskill
 };
@@ -486,10 +508,15 @@ inline void fold_rows(RowsData& d, const BPMatrixOptions& opts) {
   if (opts.alifold || opts.contrafold)
     throw "only the FOLD and SFOLD methods (McCaskill or sampled structures per row) are supported by the engine";
   if (opts.n_samples > 0x7fffffffu) throw "--sampling: too many samples";
-  Engine::get().fold(erased,
-                     (opts.no_GU ? SK_FOLD_NO_GU : 0) | (opts.no_closingGU ? SK_FOLD_NO_CLOSING_GU : 0) |
-                         (opts.no_LonelyPairs ? SK_FOLD_NO_LONELY_PAIRS : 0),
-                     d.bpp, opts.n_samples, opts.sampling_seed);
+  const int flags = (opts.no_GU ? SK_FOLD_NO_GU : 0) | (opts.no_closingGU ? SK_FOLD_NO_CLOSING_GU : 0) |
+                    (opts.no_LonelyPairs ? SK_FOLD_NO_LONELY_PAIRS : 0);
+  if (opts.consensus && opts.n_samples == 0) {
+    d.bpp.emplace_back();
+    Engine::get().fold_alignment(d.rows, flags, d.bpp.back());
+    d.consensus = true;
+    return;
+  }
+  Engine::get().fold(erased, flags, d.bpp, opts.n_samples, opts.sampling_seed);
 }
 
 inline void add_rows(sk_dataset* ds, const std::string& label, const RowsData& d, float th) {
@@ -497,6 +524,10 @@ inline void add_rows(sk_dataset* ds, const std::string& label, const RowsData& d
   std::vector<const double*> b;
   for (const auto& s : d.rows) r.push_back(s.c_str());
   for (const auto& v : d.bpp) b.push_back(v.data());
+  if (d.use_bp && d.consensus) {
+    check(sk_dataset_add_consensus(ds, label.c_str(), (int)r.size(), r.data(), b.at(0), th));
+    return;
+  }
   check(sk_dataset_add(ds, label.c_str(), (int)r.size(), r.data(), d.use_bp ? b.data() : nullptr, th,
                        d.use_bp ? 1 : 0));
 }
@@ -506,6 +537,7 @@ inline void mix_rows(Fnv& f, const RowsData& d) {
   for (const auto& b : d.bpp) f(b.data(), b.size() * sizeof(double));
   f(&d.th, sizeof(float));
   f(&d.use_bp, sizeof(bool));
+  f(&d.consensus, sizeof(bool));
 }
 
 // Example files (stem_kernel_lite/data.cpp:460-586, bpla_kernel/data.cpp:

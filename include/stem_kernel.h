@@ -342,6 +342,38 @@ int sk_fold_sample(sk_context *ctx, int32_t n, const char *const *seqs, int32_t 
 /* The sampler's generator on the host: the uniform double in [0, 1) of draw
  * number draw of sample `sample` of sequence `seq` under seed. */
 double sk_fold_sample_uniform(uint64_t seed, int32_t seq, int32_t sample, int32_t draw);
+/* Consensus (alifold-style) partition function of alignments on the GPU, one
+ * workgroup per alignment (csrc/kernels/fold_ali.hip): base-pairing
+ * probabilities of alignment COLUMNS.  Replaces BPMatrix ALIFOLD,
+ * common/bpmatrix.cpp:355-397 (ViennaRNA pf_alifold; parity unpinned like
+ * sk_fold_mccaskill's, model in DESIGN.md §9).  A consensus structure weighs
+ * exp(-(sum over rows of its energy in sk_fold_mccaskill's loop model, loop
+ * sizes in columns, - sum over its pairs of the covariance score) / (S kT)),
+ * S = rows; a column pair may form when at most half of the rows cannot pair
+ * there and its covariance score is at least -200.  rows: alignment after
+ * alignment, n_rows[k] rows of equal length each (SK_ERR_INVALID otherwise);
+ * A C G U T in any case, every other character a blank.  out: for each
+ * alignment in order, n_k(n_k-1)/2 doubles over its n_k columns in the
+ * packed layout of sk_dataset_add, concatenated.  log_z (optional): ln Z per
+ * alignment.  flags: SK_FOLD_NO_GU, SK_FOLD_NO_LONELY_PAIRS (the filter over
+ * the column pairs that may form); SK_FOLD_NO_CLOSING_GU has no per-column
+ * meaning when rows differ: SK_ERR_UNSUPPORTED.  S identical gap-free rows
+ * give sk_fold_mccaskill of that row. */
+int sk_fold_alignment(sk_context *ctx, int32_t n_aln, const int32_t *n_rows,
+                      const char *const *rows, int32_t flags, double *out, double *log_z);
+/* Append one example whose matrix is the caller's ONE matrix over the
+ * alignment's columns (bpp: len(len-1)/2 doubles, len = the rows' length;
+ * e.g. sk_fold_alignment's): the example's matrix is bpp itself, no
+ * gap-mapped average, and every row's profile reads it in alignment
+ * coordinates -- MData(ma, th, ...) when BPMatrix holds one matrix,
+ * stem_kernel_lite/data.cpp:332-339, Profiler :109-121. */
+int sk_dataset_add_consensus(sk_dataset *ds, const char *label, int n_rows,
+                             const char *const *rows, const double *bpp, float th);
+/* sk_dataset_add_folded with one sk_fold_alignment matrix per example in
+ * place of the averaged per-row folds (BPMatrix ALIFOLD). */
+int sk_dataset_add_alifolded(sk_context *ctx, sk_dataset *ds, int32_t n, int32_t n_rows,
+                             const char *const *rows, const char *const *labels, float th,
+                             int32_t fold_flags, int32_t n_threads);
 /* n examples of n_rows equal-length rows (rows[i*n_rows + r]), built on
  * n_threads host threads (0 = hardware concurrency) from the caller's
  * per-row bpp (bpp_rows[i*n_rows + r], layout of sk_dataset_add; ignored

@@ -44,7 +44,12 @@
 //     each gap-erased, lowercased row with it (honouring --noGU and
 //     --noClosingGU, --noLonelyPairs; --use-alifold is refused) and
 //     averages alignment rows as the reference does
-//     (common/bpmatrix.cpp:306-342).  Options::n_samples > 0 (SFOLD,
+//     (common/bpmatrix.cpp:306-342).  Options::consensus (the engine's own,
+//     --consensus-fold) folds each alignment as one instead: the consensus
+//     partition function over its columns (sk_fold_alignment, the engine's
+//     model in place of pf_alifold), one matrix in alignment
+//     coordinates as in the reference's ALIFOLD branch
+//     (common/bpmatrix.cpp:355-397, data.cpp:332-339).  Options::n_samples > 0 (SFOLD,
 //     --sampling N, common/bpmatrix.cpp:179-232) gives the pair frequencies
 //     of that many structures sampled on the GPU (sk_fold_sample),
 //     reproducible from Options::sampling_seed where the reference seeds

@@ -90,6 +90,10 @@ SIGNATURES = {
     "sk_fold_sample": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_char_p), C.c_int32, C.c_int32, C.c_uint64,
                                  _F64P, C.c_void_p, _F64P]),
     "sk_fold_sample_uniform": (C.c_double, [C.c_uint64, C.c_int32, C.c_int32, C.c_int32]),
+    "sk_fold_alignment": (C.c_int, [_P, C.c_int32, _I32P, C.POINTER(C.c_char_p), C.c_int32, _F64P, _F64P]),
+    "sk_dataset_add_consensus": (C.c_int, [_P, C.c_char_p, C.c_int, C.POINTER(C.c_char_p), _F64P, C.c_float]),
+    "sk_dataset_add_alifolded": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.POINTER(C.c_char_p),
+                                           C.POINTER(C.c_char_p), C.c_float, C.c_int32, C.c_int32]),
     "sk_dataset_add_sampled": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.POINTER(C.c_char_p),
                                          C.POINTER(C.c_char_p), C.c_float, C.c_int32, C.c_int32,
                                          C.c_uint64, C.c_int32]),

@@ -19,7 +19,8 @@
 // engine's GPU McCaskill (sk_fold_mccaskill) instead of ViennaRNA;
 // --sampling N (BPMatrix SFOLD) draws its structures on the GPU
 // (sk_fold_sample) from --sampling-seed, the engine's own option, instead of
-// the clock; --use-alifold is refused; .bz2 output goes through the
+// the clock; --use-alifold is refused, --consensus-fold (the engine's own)
+// folds each alignment as one (sk_fold_alignment); .bz2 output goes through the
 // system's libbz2.so.1 (loaded at run time: the image has the library but not
 // its headers).  The
 // reference's default kernel (SuStemStr without --log) only estimates memory
@@ -102,7 +103,8 @@ const char* kUsage =
     "  --noGU                      disallow GU wobble base-pairs\n"
     "  --noClosingGU               disallow closing GU base-pairs\n"
     "  --noLonelyPairs             disallow lonely base-pairs\n"
-    "  --use-alifold               use pf_alifold (not supported by the engine)\n"
+    "  --use-alifold               use pf_alifold (not supported by the engine: see --consensus-fold)\n"
+    "  --consensus-fold            fold each alignment as one: the engine's consensus partition function\n"
     "  --pf-scale                  calculate appropriciate pf_scales using MFE (no effect)\n"
     "  --sampling arg (=0)         use stochastic sampling for producing base pairing probability\n"
     "                              matrices\n"
@@ -158,6 +160,7 @@ bool parse(int argc, char** argv, Options& o, std::vector<std::string>& extra, b
       {"noClosingGU", 0, false, [&](const std::string&) { o.bp.no_closingGU = true; }},
       {"noLonelyPairs", 0, false, [&](const std::string&) { o.bp.no_LonelyPairs = true; }},
       {"use-alifold", 0, false, [&](const std::string&) { o.bp.alifold = true; }},
+      {"consensus-fold", 0, false, [&](const std::string&) { o.bp.consensus = true; }},
       {"pf-scale", 0, false, [&](const std::string&) { o.bp.use_pf_scale_mfe = true; }},
       {"sampling", 0, true, [&](const std::string& v) { o.bp.n_samples = to_uint(v); }},
       {"sampling-seed", 0, true, [&](const std::string& v) { o.bp.sampling_seed = to_u64(v); }},
@@ -592,7 +595,8 @@ int main(int argc, char** argv) {
   try {
     if (o.predict_output.size() > o.trained_model_file.size())
       throw "--predict: every prediction file needs the --model of the same position";
-    if (o.bp.alifold) throw "--use-alifold is not supported by the engine's fold";
+    if (o.bp.alifold)
+      throw "--use-alifold is not supported by the engine's fold (--consensus-fold is the engine's consensus fold)";
     if (o.predict_mode && !o.trained_model_file.empty()) load_sv_index(o.sv_index, o.trained_model_file);
     // kernel choice: main.cpp:166-214
     if (!o.no_string && !o.no_ribosum) {

@@ -233,7 +233,7 @@ class DagBuilder {
 }  // namespace
 
 void build_example(Example& ex, int n_rows, const char* const* rows,
-                   const double* const* bpp_rows, float th, bool use_bp) {
+                   const double* const* bpp_rows, float th, bool use_bp, bool consensus) {
   if (n_rows <= 0) throw std::invalid_argument("example without rows");
   ex = Example();
   ex.n_rows = n_rows;
@@ -260,10 +260,13 @@ void build_example(Example& ex, int n_rows, const char* const* rows,
   ex.bpf_off.assign(1, 0);
   if (!use_bp) return;
 
-  // averaged matrix over the aligned columns (rows summed in order, then /n)
+  // averaged matrix over the aligned columns (rows summed in order, then /n);
+  // consensus: the caller's matrix of the columns itself (BPMatrix ALIFOLD,
+  // common/bpmatrix.cpp:355-397: one matrix, no gap mapping)
   ex.bpp.assign(L > 1 ? (size_t)L * (L - 1) / 2 : 0, 0.0);
+  if (consensus) std::copy(bpp_rows[0], bpp_rows[0] + ex.bpp.size(), ex.bpp.begin());
   std::vector<BpView> row_views(n_rows);
-  for (int r = 0; r < n_rows; ++r) {
+  for (int r = 0; !consensus && r < n_rows; ++r) {
     std::vector<int> map(L, -1);
     int nr = 0;
     for (int i = 0; i < L; ++i)
@@ -275,11 +278,12 @@ void build_example(Example& ex, int n_rows, const char* const* rows,
         if (map[i] >= 0) ex.bpp[tri_index(L, i, j)] += row_views[r](map[i] + 1, map[j] + 1);
     }
   }
-  for (double& v : ex.bpp) v = v / n_rows;
+  if (!consensus)
+    for (double& v : ex.bpp) v = v / n_rows;
   const BpView avg{ex.bpp.data(), L};
 
   std::vector<RowProfile> prof(n_rows);
-  for (int r = 0; r < n_rows; ++r) prof[r].init(ex.rows[r], n_rows > 1 ? row_views[r] : avg);
+  for (int r = 0; r < n_rows; ++r) prof[r].init(ex.rows[r], n_rows > 1 && !consensus ? row_views[r] : avg);
 
   DagBuilder(prof, avg, th, ex).run();
 

@@ -51,8 +51,11 @@ struct Example {
 
 // Builds an Example from aligned rows and per-row (gap-erased) bpp matrices.
 // Restates MData(ma, th, ...) (stem_kernel_lite/data.cpp:324-345).
+// consensus: bpp_rows[0] is ONE matrix in alignment coordinates (a consensus
+// fold's), taken as the example's matrix itself and given to every row's
+// profile: the reference's n_matrices() == 1 branch (data.cpp:332-339).
 void build_example(Example& ex, int n_rows, const char* const* rows,
-                   const double* const* bpp_rows, float th, bool use_bp);
+                   const double* const* bpp_rows, float th, bool use_bp, bool consensus = false);
 
 // synth.cpp
 uint64_t splitmix64_next(uint64_t& s);

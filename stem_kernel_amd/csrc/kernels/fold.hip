@@ -26,34 +26,6 @@
 
 namespace sk {
 
-// block-wide sum (at most 8 waves), result in every thread
-__device__ __forceinline__ double block_sum(double v, double* red) {
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  const int w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[w] = v;
-  __syncthreads();
-  double s = 0.0;
-  for (int k = 0; k < nw; ++k) s += red[k];
-  return s;
-}
-
-// sum over a team of G (1, 2, 4, 8) adjacent lanes, in every lane of the team
-__device__ __forceinline__ double team_sum(double v, int G) {
-  if (G >= 2) v += __shfl_xor(v, 1, 64);
-  if (G >= 4) v += __shfl_xor(v, 2, 64);
-  if (G >= 8) v += __shfl_xor(v, 4, 64);
-  return v;
-}
-
-// lanes per cell of a span of ncell cells: the most (up to 8) that keep
-// every cell of the span in one pass of the block's threads
-__device__ __forceinline__ int team_of(int ncell, int nt) {
-  int G = 1;
-  while (G < 8 && ncell * (2 * G) <= nt) G *= 2;
-  return G;
-}
-
 // Tables are stored by DIAGONAL: cell (i, i+d) of a table at d*n + i.  A
 // span's cells are the threads (consecutive i), and every read of a loop
 // iteration sits at a fixed offset from the cell -- (i+a, j-b) lies on
@@ -63,7 +35,6 @@ __device__ __forceinline__ int team_of(int ncell, int nt) {
 // (the 31 diagonals below the span inside, above it outside) are also kept
 // in an LDS ring of kFoldRing diagonals when the sequences are short enough
 // (RING: 33 n doubles), and the Boltzmann tables and the codes sit in LDS.
-constexpr int kFoldRing = 33;  // 31 diagonals read + the one written, distinct slots
 
 // 512 threads (8 waves; 94 VGPRs: two workgroups per CU by LDS at L = 200)
 // GTAB: the hairpin and scale tables (the tail of P.tab, sized by the

@@ -1,19 +1,18 @@
 // Device pieces of the McCaskill loop model shared by the fold kernel
 // (fold.hip) and the structure sampler (fold_sample.hip): the sampler's
 // candidates are the terms of the fold's inside sums, so both must read the
-// same pair types and loop factors.
+// same pair types and loop factors.  The block / team sums and the ring size
+// are shared with the consensus fold (fold_ali.hip), whose passes are the
+// fold's.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
-namespace sk {
+#include "fold_ali_model.h"  // kFoldPairBits: the pair-type table
 
-// pair type of codes (a, b), a * 4 + b -> 4 bits of a 64-bit constant (no
-// memory access: a __constant__ table indexed per thread is a vector load):
-// {0,0,0,5, 0,0,1,0, 0,2,0,4, 6,0,3,0}  CG1 GC2 GU3 UG4 AU5 UA6
-constexpr uint64_t kFoldPairBits = 0x306402001005000ull;
+namespace sk {
 
 struct FoldTables {  // views into P.tab (FoldLaunch::tab layout)
   const double *st, *hp, *bu, *in, *ni, *au, *scp;
@@ -41,5 +40,36 @@ __device__ __forceinline__ double fold_interior(const FoldTables& T, int t1, int
   if (n1 == 0 || n2 == 0) return n == 1 ? T.bu[1] * T.st[t1 * 7 + t2] : T.bu[n] * T.au[t1] * T.au[t2];
   return T.in[n] * T.ni[abs(n1 - n2)] * T.au[t1] * T.au[t2];
 }
+
+// block-wide sum (at most 8 waves), result in every thread
+__device__ __forceinline__ double block_sum(double v, double* red) {
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  const int w = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[w] = v;
+  __syncthreads();
+  double s = 0.0;
+  for (int k = 0; k < nw; ++k) s += red[k];
+  return s;
+}
+
+// sum over a team of G (1, 2, 4, 8) adjacent lanes, in every lane of the team
+__device__ __forceinline__ double team_sum(double v, int G) {
+  if (G >= 2) v += __shfl_xor(v, 1, 64);
+  if (G >= 4) v += __shfl_xor(v, 2, 64);
+  if (G >= 8) v += __shfl_xor(v, 4, 64);
+  return v;
+}
+
+// lanes per cell of a span of ncell cells: the most (up to 8) that keep
+// every cell of the span in one pass of the block's threads
+__device__ __forceinline__ int team_of(int ncell, int nt) {
+  int G = 1;
+  while (G < 8 && ncell * (2 * G) <= nt) G *= 2;
+  return G;
+}
+
+// LDS ring of the interior-loop window (fold.hip, fold_ali.hip)
+constexpr int kFoldRing = 33;  // 31 diagonals read + the one written, distinct slots
 
 }  // namespace sk

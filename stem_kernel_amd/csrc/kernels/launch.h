@@ -330,6 +330,26 @@ constexpr int32_t kFoldSampleStack = 3;     // more open segments than n / 2 + 4
 size_t fold_sample_lds_bytes(const FoldLaunch& P, int max_n);
 hipError_t launch_fold_sample(const FoldSampleLaunch& P, int n_seqs, int max_n, hipStream_t st);
 
+// Consensus fold of alignments (fold_ali.hip): one workgroup per alignment,
+// the fold's passes over per-cell tables a first phase fills from the rows
+struct FoldAliSeq {
+  int64_t row_off = 0;   // into codes: n_rows rows of n codes
+  int64_t work_off = 0;  // into F.work: fold_ali_work_doubles(n)
+  int64_t out_off = 0;   // into F.out: n (n - 1) / 2 packed probabilities
+  int64_t lp_off = 0;    // into F.lp (--noLonelyPairs): n x n filter over the allowed column pairs
+  int32_t n = 0, n_rows = 0;
+};
+struct FoldAliLaunch {
+  FoldLaunch F;  // tab and its offsets, log_sc, no_gu, lp, work, out, log_z (seqs and codes unused)
+  const FoldAliSeq* alns = nullptr;
+  const int8_t* codes = nullptr;  // A C G U = 0..3, blank -1
+  int32_t o_ali = 0;              // in F.tab: 8 x 8 stack energies by energy type, then kT, TerminalAU, bulge(1)
+};
+constexpr int kFoldAliTabExtra = 64 + 3;
+size_t fold_ali_lds_bytes(const FoldLaunch& F, int max_n);
+inline size_t fold_ali_work_doubles(size_t n) { return 10 * n * n + 2 * (n + 1); }
+hipError_t launch_fold_ali(const FoldAliLaunch& P, int n_alns, int max_n, hipStream_t st);
+
 enum CombineMode : int32_t {
   kCombineStem = 0,      // K = stem
   kCombineStr = 1,       // K = str

@@ -28,6 +28,7 @@
 
 #include "../../include/stem_kernel.h"
 #include "host/fold_params.h"
+#include "kernels/fold_ali_model.h"
 #include "kernels/fold_rng.h"
 #include "host/sk_internal.h"
 #include "kernels/device_set.h"
@@ -3503,6 +3504,24 @@ int sk_dataset_add(sk_dataset* ds, const char* label, int n_rows, const char* co
   return SK_OK;
 }
 
+int sk_dataset_add_consensus(sk_dataset* ds, const char* label, int n_rows, const char* const* rows,
+                             const double* bpp, float th) {
+  if (!ds || n_rows <= 0 || !rows || !bpp) return SK_ERR_INVALID;
+  if (ds->uploaded) return SK_ERR_INVALID;
+  try {
+    Example ex;
+    sk::build_example(ex, n_rows, rows, &bpp, th, true, true);
+    ds->ex.push_back(std::move(ex));
+    ds->labels.emplace_back(label ? label : "");
+  } catch (const std::bad_alloc&) {
+    return SK_ERR_ALLOC;
+  } catch (const std::exception& e) {
+    ds->err = e.what();
+    return SK_ERR_INVALID;
+  }
+  return SK_OK;
+}
+
 int sk_dataset_add_copy(sk_dataset* dst, const sk_dataset* src, int32_t i) {
   if (!dst || !src || i < 0 || (size_t)i >= src->ex.size()) return SK_ERR_INVALID;
   if (dst->uploaded) return SK_ERR_INVALID;
@@ -4107,26 +4126,32 @@ int8_t fold_code(char ch) {
 // its outer neighbour cannot pair; the outer type is re-read only inside the
 // sequence, so a chain's outermost pair compares against its own type.
 // lp[i*n + j] = 1 where the pair survives (codes: fold_code, -1 never pairs).
-void lonely_pair_table(const int8_t* c, int n, bool no_gu, uint8_t* lp) {
-  static const int8_t pt[16] = {0, 0, 0, 5, 0, 0, 1, 0, 0, 2, 0, 4, 6, 0, 3, 0};
-  auto raw = [&](int i, int j) {
-    const int t = (c[i] < 0 || c[j] < 0) ? 0 : pt[c[i] * 4 + c[j]];
-    return (no_gu && (t == 3 || t == 4)) ? 0 : t;
-  };
+// (can(i, j): whether the pair can form at all; the consensus fold walks its
+// allowed column pairs)
+extern "C++" template <class Can>
+static void lonely_pair_walk(int n, Can can, uint8_t* lp) {
   std::fill(lp, lp + (size_t)n * n, (uint8_t)0);
   for (int k = 0; k < n; ++k)
     for (int l = 1; l <= 2; ++l) {
       int i = k, j = k + 3 + l, otype = 0, ntype = 0;
       if (j >= n) continue;
-      int type = raw(i, j);
+      int type = can(i, j);
       for (; i >= 0 && j < n; --i, ++j) {
-        if (i > 0 && j < n - 1) ntype = raw(i - 1, j + 1);
+        if (i > 0 && j < n - 1) ntype = can(i - 1, j + 1);
         if (!otype && !ntype) type = 0;
         lp[(size_t)i * n + j] = type != 0;
         otype = type;
         type = ntype;
       }
     }
+}
+
+void lonely_pair_table(const int8_t* c, int n, bool no_gu, uint8_t* lp) {
+  static const int8_t pt[16] = {0, 0, 0, 5, 0, 0, 1, 0, 0, 2, 0, 4, 6, 0, 3, 0};
+  lonely_pair_walk(n, [&](int i, int j) {
+    const int t = (c[i] < 0 || c[j] < 0) ? 0 : pt[c[i] * 4 + c[j]];
+    return (no_gu && (t == 3 || t == 4)) ? 0 : (int)t;
+  }, lp);
 }
 
 namespace {
@@ -4137,6 +4162,28 @@ struct FoldSampling {
   uint64_t seed = 0;
   char* structs = nullptr;  // optional, sk_fold_sample's out_structs
 };
+
+// Batches of the fold calls (sk_fold_mccaskill, sk_fold_sample,
+// sk_fold_alignment): the device memory one batch's tables may take ...
+int fold_budget(sk_context* ctx, double* budget) {
+  size_t free_b = 0, total_b = 0;
+  SK_HIP(ctx, hipMemGetInfo(&free_b, &total_b));
+  *budget = std::min(16e9, 0.4 * (double)free_b);
+  return SK_OK;
+}
+// ... and the end of the batch that starts at item b0: the items whose bytes
+// (bytes(k)) fit the budget together, at least one
+extern "C++" template <class Bytes>
+int32_t fold_batch_end(int32_t b0, int32_t n, double budget, Bytes bytes) {
+  double sum = 0.0;
+  int32_t b1 = b0;
+  for (; b1 < n; ++b1) {
+    const double w = bytes(b1);
+    if (b1 > b0 && sum + w > budget) break;
+    sum += w;
+  }
+  return b1;
+}
 
 // sk_fold_mccaskill (sm == nullptr: out gets the McCaskill probabilities) and
 // sk_fold_sample (out, optional, gets count / n_samples): the batches, their
@@ -4158,9 +4205,8 @@ int fold_run(sk_context* ctx, int32_t n, const char* const* seqs, int32_t flags,
   std::vector<double> tab;
   L.no_gu = (flags & SK_FOLD_NO_GU) ? 1 : 0;
   L.no_closing_gu = (flags & SK_FOLD_NO_CLOSING_GU) ? 1 : 0;
-  size_t free_b = 0, total_b = 0;
-  SK_HIP(ctx, hipMemGetInfo(&free_b, &total_b));
-  const double budget = std::min(16e9, 0.4 * (double)free_b);
+  double budget = 0.0;
+  if (int rc = fold_budget(ctx, &budget)) return rc;
   hipStream_t S = ctx->stream;
   size_t out_host = 0;  // packed output offset of sequence k (host)
   size_t str_host = 0;  // sampled structures written so far (host)
@@ -4170,20 +4216,20 @@ int fold_run(sk_context* ctx, int32_t n, const char* const* seqs, int32_t flags,
     std::vector<int8_t> codes;
     std::vector<uint8_t> lp;  // --noLonelyPairs tables
     size_t work = 0, outn = 0;
-    int32_t b1 = b0;
+    // (the sampled structures of the batch count too: n_samples chars per nucleotide)
+    const int32_t b1 = fold_batch_end(b0, n, budget, [&](int32_t k) {
+      return (double)sk::fold_work_doubles((size_t)len[k]) * 8.0 + (want_str ? (double)len[k] * (double)ns : 0.0);
+    });
     int bmax = 0;
-    for (; b1 < n; ++b1) {
-      const size_t nn = (size_t)len[b1];
+    for (int32_t k = b0; k < b1; ++k) {
+      const size_t nn = (size_t)len[k];
       const size_t w = sk::fold_work_doubles(nn);
-      // (the sampled structures of the batch count too: n_samples chars per nucleotide)
-      const double strb = want_str ? (double)(codes.size() + nn) * (double)ns : 0.0;
-      if (!sq.empty() && (double)(work + w) * 8.0 + strb > budget) break;
       sk::FoldSeq f;
       f.seq_off = (int64_t)codes.size();
       f.work_off = (int64_t)work;
       f.out_off = (int64_t)outn;
       f.n = (int32_t)nn;
-      for (size_t a = 0; a < nn; ++a) codes.push_back(fold_code(seqs[b1][a]));
+      for (size_t a = 0; a < nn; ++a) codes.push_back(fold_code(seqs[k][a]));
       if (no_lp) {
         f.lp_off = (int64_t)lp.size();
         lp.resize(lp.size() + nn * nn);
@@ -4306,13 +4352,149 @@ double sk_fold_sample_uniform(uint64_t seed, int32_t seq, int32_t sample, int32_
   return sk::rng_uniform(sk::rng_stream(seed, seq, sample), draw);
 }
 
+// ---------------------------------------------------------------- consensus fold
+namespace {
+// --noLonelyPairs of the consensus fold: lonely_pair_table's walk over the
+// column pairs the covariance score allows (c: n_rows rows of n codes)
+void lonely_pair_table_ali(const int8_t* c, int n_rows, int n, bool no_gu, uint8_t* lp) {
+  std::vector<uint8_t> ok((size_t)n * n, 0);
+  for (int i = 0; i < n; ++i)
+    for (int j = i + 4; j < n; ++j) {
+      sk::AliCounts pf;
+      for (int s = 0; s < n_rows; ++s) pf.add(sk::ali_row_type(c[(size_t)s * n + i], c[(size_t)s * n + j], no_gu));
+      int64_t ps = 0;
+      ok[(size_t)i * n + j] = sk::ali_allowed(pf, n_rows, j - i, &ps);
+    }
+  lonely_pair_walk(n, [&](int i, int j) { return (int)ok[(size_t)i * n + j]; }, lp);
+}
+}  // namespace
+
+int sk_fold_alignment(sk_context* ctx, int32_t n_aln, const int32_t* n_rows, const char* const* rows,
+                      int32_t flags, double* out, double* log_z) {
+  if (!ctx || n_aln < 0 || (n_aln > 0 && (!n_rows || !rows || !out))) return fail(ctx, SK_ERR_INVALID, "null argument");
+  if (flags & ~(SK_FOLD_NO_GU | SK_FOLD_NO_CLOSING_GU | SK_FOLD_NO_LONELY_PAIRS))
+    return fail(ctx, SK_ERR_UNSUPPORTED, "fold: unknown flag");
+  if (flags & SK_FOLD_NO_CLOSING_GU)
+    return fail(ctx, SK_ERR_UNSUPPORTED,
+                "consensus fold: --noClosingGU has no per-column meaning when the rows differ");
+  if (n_aln == 0) return SK_OK;
+  const bool no_lp = (flags & SK_FOLD_NO_LONELY_PAIRS) != 0;
+  std::vector<int> len(n_aln);
+  std::vector<size_t> first(n_aln + 1, 0);  // first row of alignment k in rows
+  for (int32_t k = 0; k < n_aln; ++k) {
+    if (n_rows[k] < 1) return fail(ctx, SK_ERR_INVALID, "consensus fold: an alignment needs at least one row");
+    if (n_rows[k] > sk::kAliMaxRows) return fail(ctx, SK_ERR_UNSUPPORTED, "consensus fold: too many rows");
+    first[k + 1] = first[k] + (size_t)n_rows[k];
+    for (size_t r = first[k]; r < first[k + 1]; ++r) {
+      if (!rows[r]) return fail(ctx, SK_ERR_INVALID, "null row");
+      const int m = (int)std::strlen(rows[r]);
+      if (r == first[k]) len[k] = m;
+      else if (m != len[k]) return fail(ctx, SK_ERR_INVALID, "consensus fold: rows of unequal length");
+    }
+  }
+  sk::FoldAliLaunch L;
+  std::vector<double> tab;
+  L.F.no_gu = (flags & SK_FOLD_NO_GU) ? 1 : 0;
+  double budget = 0.0;
+  if (int rc = fold_budget(ctx, &budget)) return rc;
+  hipStream_t S = ctx->stream;
+  size_t out_host = 0;
+  for (int32_t b0 = 0; b0 < n_aln;) {
+    const int32_t b1 = fold_batch_end(b0, n_aln, budget, [&](int32_t k) {
+      const double nn = (double)len[k];
+      return (double)sk::fold_ali_work_doubles((size_t)len[k]) * 8.0 + nn * (double)n_rows[k] + (no_lp ? nn * nn : 0.0);
+    });
+    std::vector<sk::FoldAliSeq> sq;
+    std::vector<int8_t> codes;
+    std::vector<uint8_t> lp;
+    size_t work = 0, outn = 0;
+    int bmax = 0;
+    for (int32_t k = b0; k < b1; ++k) {
+      const size_t nn = (size_t)len[k];
+      sk::FoldAliSeq f;
+      f.row_off = (int64_t)codes.size();
+      f.work_off = (int64_t)work;
+      f.out_off = (int64_t)outn;
+      f.n = (int32_t)nn;
+      f.n_rows = n_rows[k];
+      for (size_t r = first[k]; r < first[k + 1]; ++r)
+        for (size_t a = 0; a < nn; ++a) codes.push_back(fold_code(rows[r][a]));
+      if (no_lp) {
+        f.lp_off = (int64_t)lp.size();
+        lp.resize(lp.size() + nn * nn);
+        lonely_pair_table_ali(codes.data() + f.row_off, n_rows[k], (int)nn, L.F.no_gu != 0, lp.data() + f.lp_off);
+      }
+      work += sk::fold_ali_work_doubles(nn);
+      outn += nn > 1 ? nn * (nn - 1) / 2 : 0;
+      bmax = std::max(bmax, (int)nn);
+      sq.push_back(f);
+    }
+    const int nb = b1 - b0;
+    // the fold's tables, then the energies the per-cell phase sums over the rows
+    fold_tables(bmax, L.F, tab);
+    L.o_ali = (int32_t)tab.size();
+    for (int a = 0; a < 8; ++a)
+      for (int b = 0; b < 8; ++b)
+        tab.push_back(a >= 1 && a <= 6 && b >= 1 && b <= 6 ? (double)sk::foldp::stack37[a][b] : 0.0);
+    tab.push_back(sk::foldp::kT);
+    tab.push_back((double)sk::foldp::terminal_au);
+    tab.push_back((double)sk::foldp::bulge37[1]);
+    L.F.n_tab = (int32_t)tab.size();
+    L.F.n_tab_pad = (L.F.n_tab + 1) & ~1;
+    if (sk::fold_ali_lds_bytes(L.F, bmax) > sk::kFoldLdsMax)
+      return fail(ctx, SK_ERR_UNSUPPORTED, "consensus fold: alignment too long for the kernel's LDS");
+    const size_t need = sq.size() * sizeof(sk::FoldAliSeq) + codes.size() + lp.size() + tab.size() * 8 +
+                        (outn + nb) * 8 + 10 * 256;
+    int rc = ensure_work(ctx, need);
+    if (rc) return rc;
+    rc = ensure_scratch(ctx, std::max<size_t>(work * 8, 64));
+    if (rc) return rc;
+    Arena A{static_cast<char*>(ctx->work), 0, ctx->work_bytes};
+    sk::FoldAliSeq* d_sq = A.take<sk::FoldAliSeq>(sq.size());
+    int8_t* d_codes = A.take<int8_t>(std::max<size_t>(codes.size(), 1));
+    double* d_tab = A.take<double>(tab.size());
+    double* d_out = A.take<double>(std::max<size_t>(outn, 1));
+    double* d_lz = A.take<double>(nb);
+    uint8_t* d_lp = no_lp ? A.take<uint8_t>(std::max<size_t>(lp.size(), 1)) : nullptr;
+    if (no_lp && !lp.empty()) SK_HIP(ctx, hipMemcpyAsync(d_lp, lp.data(), lp.size(), hipMemcpyHostToDevice, S));
+    SK_HIP(ctx, hipMemcpyAsync(d_sq, sq.data(), sq.size() * sizeof(sk::FoldAliSeq), hipMemcpyHostToDevice, S));
+    if (!codes.empty())
+      SK_HIP(ctx, hipMemcpyAsync(d_codes, codes.data(), codes.size(), hipMemcpyHostToDevice, S));
+    SK_HIP(ctx, hipMemcpyAsync(d_tab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, S));
+    SK_HIP(ctx, hipMemsetAsync(ctx->scratch, 0, work * 8, S));
+    SK_HIP(ctx, hipMemsetAsync(d_out, 0, std::max<size_t>(outn, 1) * 8, S));
+    L.F.lp = d_lp;
+    L.F.tab = d_tab;
+    L.F.work = ctx->scratch;
+    L.F.out = d_out;
+    L.F.log_z = d_lz;
+    L.alns = d_sq;
+    L.codes = d_codes;
+    SK_HIP(ctx, sk::launch_fold_ali(L, nb, bmax, S));
+    std::vector<double> lz(nb);
+    if (outn) SK_HIP(ctx, hipMemcpyAsync(out + out_host, d_out, outn * 8, hipMemcpyDeviceToHost, S));
+    SK_HIP(ctx, hipMemcpyAsync(lz.data(), d_lz, nb * 8, hipMemcpyDeviceToHost, S));
+    SK_HIP(ctx, hipStreamSynchronize(S));
+    for (int k = 0; k < nb; ++k) {
+      if (!std::isfinite(lz[k]))
+        return fail(ctx, SK_ERR_UNSUPPORTED,
+                    "consensus fold: partition function out of double range (alignment too long)");
+      if (log_z) log_z[b0 + k] = lz[k];
+    }
+    out_host += outn;
+    b0 = b1;
+  }
+  return SK_OK;
+}
+
 namespace {
 // Threaded DAG builds of n examples of n_rows rows from per-row bpp (caller's
 // or folded), appended to ds; the parallel form of the reference's load loop
 // (common/framework.h:308-353 + DataLoader<MData>::get, data.cpp:548-586).
+// (consensus: bpp_rows[i] is example i's one matrix in alignment coordinates)
 int add_examples_threaded(sk_dataset* ds, int32_t n, int32_t n_rows, const char* const* rows,
                           const double* const* bpp_rows, const char* const* labels, float th,
-                          int use_bp, int32_t n_threads) {
+                          int use_bp, int32_t n_threads, bool consensus = false) {
   const size_t base = ds->ex.size();
   try {
     ds->ex.resize(base + n);
@@ -4329,7 +4511,8 @@ int add_examples_threaded(sk_dataset* ds, int32_t n, int32_t n_rows, const char*
       if (i >= n || status.load() != SK_OK) return;
       try {
         sk::build_example(ds->ex[base + i], n_rows, rows + (size_t)i * n_rows,
-                          use_bp ? bpp_rows + (size_t)i * n_rows : nullptr, th, use_bp != 0);
+                          use_bp ? bpp_rows + (size_t)i * (consensus ? 1 : n_rows) : nullptr, th, use_bp != 0,
+                          consensus);
       } catch (...) {
         status.store(SK_ERR_INVALID);
       }
@@ -4395,6 +4578,28 @@ int sk_dataset_add_sampled(sk_context* ctx, sk_dataset* ds, int32_t n, int32_t n
                            int32_t fold_flags, int32_t n_samples, uint64_t seed, int32_t n_threads) {
   if (n_samples < 1) return fail(ctx, SK_ERR_INVALID, "fold sampling: n_samples must be at least 1");
   return add_folded(ctx, ds, n, n_rows, rows, labels, th, fold_flags, n_samples, seed, n_threads);
+}
+
+int sk_dataset_add_alifolded(sk_context* ctx, sk_dataset* ds, int32_t n, int32_t n_rows,
+                             const char* const* rows, const char* const* labels, float th,
+                             int32_t fold_flags, int32_t n_threads) {
+  if (!ctx || !ds || n < 0 || n_rows < 1 || (n > 0 && !rows)) return fail(ctx, SK_ERR_INVALID, "null argument");
+  if (ds->uploaded) return fail(ctx, SK_ERR_INVALID, "dataset already uploaded");
+  // one consensus matrix per example, in alignment coordinates
+  std::vector<size_t> off((size_t)n + 1, 0);
+  for (int32_t i = 0; i < n; ++i) {
+    if (!rows[(size_t)i * n_rows]) return fail(ctx, SK_ERR_INVALID, "null row");
+    const size_t m = std::strlen(rows[(size_t)i * n_rows]);
+    off[i + 1] = off[i] + (m > 1 ? m * (m - 1) / 2 : 0);
+  }
+  std::vector<double> bpp(std::max<size_t>(off[n], 1));
+  const std::vector<int32_t> nr((size_t)n, n_rows);
+  int rc = sk_fold_alignment(ctx, n, nr.data(), rows, fold_flags, bpp.data(), nullptr);
+  if (rc) return rc;
+  std::vector<const double*> bptr((size_t)n);
+  for (int32_t i = 0; i < n; ++i) bptr[i] = bpp.data() + off[i];
+  rc = add_examples_threaded(ds, n, n_rows, rows, bptr.data(), labels, th, 1, n_threads, true);
+  return rc ? fail(ctx, rc, "example build failed") : SK_OK;
 }
 
 int sk_random_sequences(uint64_t* state, int32_t n_seqs, int32_t len, char* out) {

@@ -250,11 +250,28 @@ class Dataset:
         return self._h
 
     def add(self, label: str, rows: Sequence[str], bpp_rows: Optional[Sequence[np.ndarray]] = None,
-            th: float = 0.01, use_bp: bool = True) -> None:
+            th: float = 0.01, use_bp: bool = True, consensus_bpp: Optional[np.ndarray] = None) -> None:
         """Append one example (an alignment of ``rows``).  ``bpp_rows[r]`` is the
         packed bp matrix of the gap-erased row r; computed with ``fold`` when
-        omitted."""
+        omitted.  ``consensus_bpp``: ONE packed matrix over the alignment's
+        columns instead (a consensus fold's, ``Context.fold_alignment``), used
+        as the example's matrix itself (sk_dataset_add_consensus)."""
         rows = list(rows)
+        if consensus_bpp is not None:
+            if bpp_rows is not None or not use_bp:
+                raise ValueError("consensus_bpp excludes bpp_rows and use_bp=False")
+            n = len(rows)
+            m = len(rows[0]) if n else 0
+            b = np.ascontiguousarray(consensus_bpp, dtype=np.float64)
+            if b.ndim != 1 or b.size != m * (m - 1) // 2:
+                raise ValueError(f"consensus_bpp needs {m * (m - 1) // 2} entries, the packed upper "
+                                 f"triangle over {m} columns; got {b.size}")
+            if b.size == 0:
+                b = np.zeros(1)
+            carr = (C.c_char_p * max(n, 1))(*[r.encode() for r in rows])
+            check(lib().sk_dataset_add_consensus(self._h, label.encode(), n, carr,
+                                                 b.ctypes.data_as(C.POINTER(C.c_double)), C.c_float(th)))
+            return
         if use_bp and bpp_rows is None:
             bpp_rows = [fold(r.replace("-", "").lower()) for r in rows]
         n = len(rows)
@@ -349,14 +366,16 @@ class Dataset:
     @classmethod
     def folded(cls, ctx: "Context", alns, labels=None, th: float = 0.01, no_gu: bool = False,
                no_closing_gu: bool = False, threads: int = 0, no_lonely_pairs: bool = False,
-               n_samples: int = 0, seed: int = 0):
+               n_samples: int = 0, seed: int = 0, consensus: bool = False):
         """Examples whose rows are folded on ctx's GPU (sk_fold_mccaskill, the
         engine's McCaskill in place of Vienna pf_fold) and built on host
         threads (sk_dataset_add_folded).  ``alns``: sequences or alignments
         of equal row count.  ``n_samples`` > 0: the bpp are the pair
         frequencies of that many sampled structures per row
         (sk_dataset_add_sampled, the reference's --sampling), reproducible
-        from ``seed``."""
+        from ``seed``.  ``consensus``: one consensus fold per alignment
+        (sk_dataset_add_alifolded) in place of the averaged per-row folds;
+        as in the reference's Options::method(), ``n_samples`` > 0 wins."""
         alns = [[a] if isinstance(a, str) else list(a) for a in alns]
         ds = cls()
         n = len(alns)
@@ -372,6 +391,9 @@ class Dataset:
         if n_samples > 0:
             ctx._chk(lib().sk_dataset_add_sampled(ctx.handle, ds._h, n, nr, rarr, larr, C.c_float(th),
                                                   flags, n_samples, seed, threads))
+        elif consensus:
+            ctx._chk(lib().sk_dataset_add_alifolded(ctx.handle, ds._h, n, nr, rarr, larr, C.c_float(th),
+                                                    flags, threads))
         else:
             ctx._chk(lib().sk_dataset_add_folded(ctx.handle, ds._h, n, nr, rarr, larr, C.c_float(th),
                                                  flags, threads))
@@ -505,6 +527,30 @@ class Context:
             res.append(out[o:o + z].copy())
             o += z
         return (res, lz[:n]) if log_z else res
+
+    def fold_alignment(self, alns: Sequence[Sequence[str]], no_gu: bool = False,
+                       no_lonely_pairs: bool = False, with_log_z: bool = False):
+        """Consensus base-pairing probabilities of the columns of every
+        alignment (a list of equal-length rows) on this GPU
+        (sk_fold_alignment): a list of packed upper triangles over the
+        columns, plus ln Z per alignment when ``with_log_z``."""
+        alns = [[a] if isinstance(a, str) else list(a) for a in alns]
+        n = len(alns)
+        sizes = [len(a[0]) * (len(a[0]) - 1) // 2 if a else 0 for a in alns]
+        out = np.zeros(max(sum(sizes), 1))
+        lz = np.zeros(max(n, 1))
+        flat = [r.encode() for a in alns for r in a]
+        rarr = (C.c_char_p * max(len(flat), 1))(*flat)
+        nrow = np.array([len(a) for a in alns] or [0], dtype=np.int32)
+        flags = (1 if no_gu else 0) | (4 if no_lonely_pairs else 0)
+        self._chk(lib().sk_fold_alignment(self._h, n, nrow.ctypes.data_as(C.POINTER(C.c_int32)), rarr, flags,
+                                          out.ctypes.data_as(C.POINTER(C.c_double)),
+                                          lz.ctypes.data_as(C.POINTER(C.c_double))))
+        res, o = [], 0
+        for z in sizes:
+            res.append(out[o:o + z].copy())
+            o += z
+        return (res, lz[:n]) if with_log_z else res
 
     def fold_sample(self, seqs: Sequence[str], n_samples: int, seed: int = 0, no_gu: bool = False,
                     no_closing_gu: bool = False, no_lonely_pairs: bool = False,
