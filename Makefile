@@ -10,10 +10,12 @@ CXXFLAGS := -O3 -std=c++17 -fPIC -Wall -Wno-unused-result -I$(ROOT)include -I$(R
 HIPFLAGS := $(CXXFLAGS) --offload-arch=$(ARCH) -munsafe-fp-atomics
 BUILD := $(ROOT)build
 LIB := $(ROOT)stem_kernel_amd/libstem_kernel_amd.so
+LINK := $(HIPCC) --offload-arch=$(ARCH) -shared -fPIC
+LINK_LIBS := -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
 
 HOST_SRC := $(ROOT)stem_kernel_amd/csrc/host/synth.cpp $(ROOT)stem_kernel_amd/csrc/host/example_build.cpp \
             $(ROOT)stem_kernel_amd/csrc/host/readers.cpp $(ROOT)stem_kernel_amd/csrc/host/shard.cpp \
-            $(ROOT)stem_kernel_amd/csrc/host/svm_predict.cpp
+            $(ROOT)stem_kernel_amd/csrc/host/svm_predict.cpp $(ROOT)stem_kernel_amd/csrc/host/fold_host.cpp
 API_SRC := $(ROOT)stem_kernel_amd/csrc/sk_api.cpp
 HIP_SRC := $(ROOT)stem_kernel_amd/csrc/kernels/dag_stem.hip $(ROOT)stem_kernel_amd/csrc/kernels/profile_string.hip \
            $(ROOT)stem_kernel_amd/csrc/kernels/bpla.hip $(ROOT)stem_kernel_amd/csrc/kernels/stem4d.hip \
@@ -52,7 +54,7 @@ $(BUILD)/kernels/bpla_grad.o: HIPFLAGS += -ffp-contract=off
 $(BUILD)/host/synth.o: CXXFLAGS += -ffp-contract=off
 
 $(LIB): $(HOST_OBJ) $(HIP_OBJ)
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
+	$(LINK) -o $@ $^ $(LINK_LIBS)
 
 oracle:
 	$(MAKE) -C $(ROOT)oracle
@@ -63,13 +65,18 @@ clean:
 
 .PHONY: all lib cli oracle clean
 
+# The diagnostic and experiment builds below recompile one or two sources with
+# extra defines and link them with the default build's other objects (make lib
+# first): $(call relink,out.so,replaced default objects,their replacements)
+relink = $(LINK) -o $(1) $(filter-out $(2),$(HOST_OBJ) $(HIP_OBJ)) $(3) $(LINK_LIBS)
+
 # diagnostic build with in-kernel phase stamps (never the shipped library)
 STAMPS_LIB := $(ROOT)build/libstem_kernel_amd_stamps.so
 stamps:
 	@mkdir -p $(BUILD)/stamps
 	$(HIPCC) $(HIPFLAGS) -DSK_STAMPS -x hip -c $(ROOT)stem_kernel_amd/csrc/kernels/dag_stem.hip -o $(BUILD)/stamps/dag_stem.o
 	$(HIPCC) $(CXXFLAGS) -DSK_STAMPS -D__HIP_PLATFORM_AMD__ -c $(API_SRC) -o $(BUILD)/stamps/sk_api.o
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $(STAMPS_LIB) $(BUILD)/host/synth.o $(BUILD)/host/example_build.o $(BUILD)/host/readers.o $(BUILD)/host/shard.o $(BUILD)/host/svm_predict.o $(BUILD)/stamps/sk_api.o $(BUILD)/stamps/dag_stem.o $(BUILD)/kernels/profile_string.o $(BUILD)/kernels/bpla.o $(BUILD)/kernels/stem4d.o $(BUILD)/kernels/phmm.o $(BUILD)/kernels/bpla_grad.o $(BUILD)/kernels/dag_stem_big.o $(BUILD)/kernels/fold.o $(BUILD)/kernels/fold_sample.o $(BUILD)/kernels/fold_ali.o -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
+	$(call relink,$(STAMPS_LIB),$(BUILD)/sk_api.o $(BUILD)/kernels/dag_stem.o,$(BUILD)/stamps/sk_api.o $(BUILD)/stamps/dag_stem.o)
 .PHONY: stamps
 
 # experiment build: make variant NAME=x DEFS="-DSK_PW=3 [-DSK_STAMPS]" -> build/libsk_x.so
@@ -77,21 +84,21 @@ variant:
 	@mkdir -p $(BUILD)/var/$(NAME)
 	$(HIPCC) $(HIPFLAGS) $(DEFS) -x hip -c $(ROOT)stem_kernel_amd/csrc/kernels/dag_stem.hip -o $(BUILD)/var/$(NAME)/dag_stem.o
 	$(HIPCC) $(CXXFLAGS) $(DEFS) -D__HIP_PLATFORM_AMD__ -c $(API_SRC) -o $(BUILD)/var/$(NAME)/sk_api.o
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $(BUILD)/libsk_$(NAME).so $(BUILD)/host/synth.o $(BUILD)/host/example_build.o $(BUILD)/host/readers.o $(BUILD)/host/shard.o $(BUILD)/host/svm_predict.o $(BUILD)/var/$(NAME)/sk_api.o $(BUILD)/var/$(NAME)/dag_stem.o $(BUILD)/kernels/profile_string.o $(BUILD)/kernels/bpla.o $(BUILD)/kernels/stem4d.o $(BUILD)/kernels/phmm.o $(BUILD)/kernels/bpla_grad.o $(BUILD)/kernels/dag_stem_big.o $(BUILD)/kernels/fold.o $(BUILD)/kernels/fold_sample.o $(BUILD)/kernels/fold_ali.o -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
+	$(call relink,$(BUILD)/libsk_$(NAME).so,$(BUILD)/sk_api.o $(BUILD)/kernels/dag_stem.o,$(BUILD)/var/$(NAME)/sk_api.o $(BUILD)/var/$(NAME)/dag_stem.o)
 .PHONY: variant
 
 # fold kernel experiment build: make variantf NAME=x DEFS="-DSK_FOLD_TIMING" -> build/libsk_x.so
 variantf:
 	@mkdir -p $(BUILD)/var/$(NAME)
 	$(HIPCC) $(HIPFLAGS) $(DEFS) -x hip -c $(ROOT)stem_kernel_amd/csrc/kernels/fold.hip -o $(BUILD)/var/$(NAME)/fold.o
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $(BUILD)/libsk_$(NAME).so $(BUILD)/host/synth.o $(BUILD)/host/example_build.o $(BUILD)/host/readers.o $(BUILD)/host/shard.o $(BUILD)/host/svm_predict.o $(BUILD)/sk_api.o $(BUILD)/kernels/dag_stem.o $(BUILD)/kernels/profile_string.o $(BUILD)/kernels/bpla.o $(BUILD)/kernels/stem4d.o $(BUILD)/kernels/phmm.o $(BUILD)/kernels/bpla_grad.o $(BUILD)/kernels/dag_stem_big.o $(BUILD)/var/$(NAME)/fold.o $(BUILD)/kernels/fold_sample.o $(BUILD)/kernels/fold_ali.o -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
+	$(call relink,$(BUILD)/libsk_$(NAME).so,$(BUILD)/kernels/fold.o,$(BUILD)/var/$(NAME)/fold.o)
 .PHONY: variantf
 
 # 4-D kernel experiment build: make variant4 NAME=x DEFS="-DSK4_MINB=4" -> build/libsk_x.so
 variant4:
 	@mkdir -p $(BUILD)/var/$(NAME)
 	$(HIPCC) $(HIPFLAGS) $(DEFS) -x hip -c $(ROOT)stem_kernel_amd/csrc/kernels/stem4d.hip -o $(BUILD)/var/$(NAME)/stem4d.o
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $(BUILD)/libsk_$(NAME).so $(BUILD)/host/synth.o $(BUILD)/host/example_build.o $(BUILD)/host/readers.o $(BUILD)/host/shard.o $(BUILD)/host/svm_predict.o $(BUILD)/sk_api.o $(BUILD)/kernels/dag_stem.o $(BUILD)/kernels/profile_string.o $(BUILD)/kernels/bpla.o $(BUILD)/var/$(NAME)/stem4d.o $(BUILD)/kernels/phmm.o $(BUILD)/kernels/bpla_grad.o $(BUILD)/kernels/dag_stem_big.o $(BUILD)/kernels/fold.o $(BUILD)/kernels/fold_sample.o $(BUILD)/kernels/fold_ali.o -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
+	$(call relink,$(BUILD)/libsk_$(NAME).so,$(BUILD)/kernels/stem4d.o,$(BUILD)/var/$(NAME)/stem4d.o)
 .PHONY: variant4
 
 # experiments build: the shipped sources with the A/B switches compiled in
@@ -105,5 +112,5 @@ $(BUILD)/exp/%.o: $(ROOT)stem_kernel_amd/csrc/%.cpp $(HDRS)
 	$(HIPCC) $(CXXFLAGS) -DSK_EXPERIMENTS -D__HIP_PLATFORM_AMD__ -c $< -o $@
 $(BUILD)/exp/host/synth.o: CXXFLAGS += -ffp-contract=off
 $(EXP_LIB): $(EXP_OBJ) $(HIP_OBJ)
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
+	$(LINK) -o $@ $^ $(LINK_LIBS)
 .PHONY: exp

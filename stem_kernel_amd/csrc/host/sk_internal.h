@@ -5,6 +5,8 @@
 #include <string>
 #include <vector>
 
+#include "tri_index.h"
+
 // Experiment switches (A/B variants of equal results, tuning knobs): read
 // from the environment only in the experiments build (make exp ->
 // build/libstem_kernel_amd_exp.so, -DSK_EXPERIMENTS); the shipped library
@@ -61,10 +63,6 @@ void build_example(Example& ex, int n_rows, const char* const* rows,
 uint64_t splitmix64_next(uint64_t& s);
 void fold_nussinov(const char* seq, int n, bool no_gu, double* out);
 void random_sequence(uint64_t& state, int len, char* out);
-
-inline size_t tri_index(int n, int i, int j) {  // 0-based i<j
-  return (size_t)i * n - (size_t)i * (i + 1) / 2 + (size_t)(j - i - 1);
-}
 
 int char2rna(int c);
 extern const float kIupac[16][4];

@@ -19,6 +19,11 @@
 // the ones read down a column.  All quantities of a subsequence carry a
 // per-nucleotide scale sc^len (Vienna's pf_scale), so Z stays in range for
 // n up to ~1,400; P(i,j) = Qb Hb / Z is scale-free.
+//
+// The passes the consensus fold (fold_ali.hip) runs too -- Qm1, Qm, the Q5 /
+// H5 sweeps, Hm, Hm1 -- the ring slots and the launch wrapper are in
+// fold_dev.h, the work-buffer layout and its cells (FoldWork) in launch.h;
+// here are the interior-loop sums and this fold's pair model (FoldPairModel).
 #include <hip/hip_runtime.h>
 
 #include "fold_dev.h"
@@ -36,7 +41,9 @@ namespace sk {
 // in an LDS ring of kFoldRing diagonals when the sequences are short enough
 // (RING: 33 n doubles), and the Boltzmann tables and the codes sit in LDS.
 
-// 512 threads (8 waves; 94 VGPRs: two workgroups per CU by LDS at L = 200)
+// 512 threads (8 waves; 100 VGPRs with the ring, 104 with the tables in HBM,
+// 108 with neither: 4 waves per SIMD, no scratch; two workgroups per CU by
+// LDS at L = 200)
 // GTAB: the hairpin and scale tables (the tail of P.tab, sized by the
 // batch's longest sequence) are read from HBM, only the fixed-size head sits
 // in LDS -- long sequences, whose tables would not fit beside the codes
@@ -47,37 +54,19 @@ __global__ void __launch_bounds__(512) sk_fold_kernel(FoldLaunch P) {
   const FoldSeq sq = P.seqs[blockIdx.x];
   const int n = sq.n;
   const int tid = threadIdx.x, nt = blockDim.x;
-  const size_t N2 = (size_t)n * n;
-  double* W = P.work + sq.work_off;
-  double *Qb = W, *Qm = W + N2, *Qm1 = W + 2 * N2, *Hb = W + 3 * N2, *Hm = W + 4 * N2, *Hm1 = W + 5 * N2;
-  double *Q5 = W + 6 * N2, *H5 = Q5 + n + 1;
+  const FoldWork w{P.work + sq.work_off, (size_t)n, kFoldTables};
   // LDS: the Boltzmann tables, the ring (RING), the codes
   double* tl = fsm;
   const int n_lds = GTAB ? P.n_small : P.n_tab;  // table entries copied to LDS
   double* ring = tl + ((n_lds + 1) & ~1);
-  int8_t* c = reinterpret_cast<int8_t*>(ring + (RING ? kFoldRing * P.ring_n : 0));
+  int8_t* c = reinterpret_cast<int8_t*>(ring + (RING ? kFoldRing * P.max_n : 0));
   for (int k = tid; k < n_lds; k += nt) tl[k] = P.tab[k];
   for (int k = tid; k < n; k += nt) c[k] = P.codes[sq.seq_off + k];
   __syncthreads();
-  FoldTables T;
-  T.st = tl + P.o_st;
-  T.hp = GTAB ? P.tab + P.o_hp : tl + P.o_hp;
-  T.bu = tl + P.o_bu;
-  T.in = tl + P.o_in;
-  T.ni = tl + P.o_ni;
-  T.au = tl + P.o_au;
-  T.scp = GTAB ? P.tab + P.o_scp : tl + P.o_scp;
-  T.mlc = tl[P.o_ml];
-  T.mli = tl[P.o_ml + 1];
+  const FoldTables T = fold_table_views(P, tl, GTAB ? P.tab : tl);
   const double* scp = T.scp;
-  const bool ngu = P.no_gu != 0, ncg = P.no_closing_gu != 0;
-  const uint8_t* __restrict__ lp = P.lp ? P.lp + sq.lp_off : nullptr;
-  auto ptype = [&](int i, int j) { return fold_ptype(c, lp, n, ngu, i, j); };
-  auto D = [&](int d, int i) { return (size_t)d * n + i; };
-  // ring slot of diagonal d, and the slot of d - 1 / d + 1 given d's
-  auto slot = [](int d) { return d % kFoldRing; };
-  auto dn = [](int sl) { return sl == 0 ? kFoldRing - 1 : sl - 1; };
-  auto up = [](int sl) { return sl == kFoldRing - 1 ? 0 : sl + 1; };
+  const bool ncg = P.no_closing_gu != 0;
+  const FoldPairModel M{c, P.lp ? P.lp + sq.lp_off : nullptr, T.au, n, P.no_gu != 0, ncg};
 #ifdef SK_FOLD_TIMING  // diagnostic build: cycles per pass, printed for blocks 0 and 1
   const uint64_t tk0 = clock64();
 #endif
@@ -95,7 +84,7 @@ __global__ void __launch_bounds__(512) sk_fold_kernel(FoldLaunch P) {
       const int i0 = base + tid / G, r = tid % G;
       const bool on = i0 < ncell;
       const int i = on ? i0 : 0, j = i + d;
-      const int t = on ? ptype(i, j) : 0;
+      const int t = on ? M.ptype(i, j) : 0;
       double part = 0.0;
       if (t) {
         // interior loops closed by (p, q) = (i+1+n1, j-1-n2), n1 + n2 <= 30,
@@ -104,10 +93,10 @@ __global__ void __launch_bounds__(512) sk_fold_kernel(FoldLaunch P) {
           const int p = i + 1 + n1;
           const int n2m = min(30 - n1, d - 6 - n1);
           const int cp = c[p];
-          int sl = slot(d - 2 - n1);
+          int sl = fold_ring_slot(d - 2 - n1);
           for (int n2 = 0; n2 <= n2m; ++n2) {
-            const double v = RING ? ring[(size_t)sl * P.ring_n + p] : Qb[D(d - 2 - n1 - n2, p)];
-            sl = dn(sl);
+            const double v = RING ? ring[(size_t)sl * P.max_n + p] : w.qb(d - 2 - n1 - n2, p);
+            sl = fold_ring_dn(sl);
             if (v != 0.0)
               part += v * fold_interior(T, t, pair_raw(c[j - 1 - n2], cp), n1, n2, ncg) * scp[n1 + n2 + 2];
           }
@@ -116,34 +105,17 @@ __global__ void __launch_bounds__(512) sk_fold_kernel(FoldLaunch P) {
           // multiloop closed by (i, j): Qm(i+1, u) Qm1(u+1, j-1), u = i+e
           double ml = 0.0;
 #pragma unroll 4
-          for (int e = 5 + r; e + 6 <= d; e += G) ml += Qm[D(e - 1, i + 1)] * Qm1[D(d - e - 2, i + e + 1)];
+          for (int e = 5 + r; e + 6 <= d; e += G) ml += w.qm(e - 1, i + 1) * w.qm1(d - e - 2, i + e + 1);
           part += ml * T.mlc * T.au[t] * scp[2];
         }
       }
       part = team_sum(part, G);
       const double qb = t ? (!(ncg && is_gu(t)) ? T.hp[d - 1] * T.au[t] * scp[d + 1] : 0.0) + part : 0.0;
       if (on && r == 0) {
-        Qb[D(d, i)] = qb;
-        if (RING) ring[(size_t)slot(d) * P.ring_n + i] = qb;
+        w.qb(d, i) = qb;
+        if (RING) ring[(size_t)fold_ring_slot(d) * P.max_n + i] = qb;
       }
-      double m1 = 0.0;  // Qm1(i, j): Qb(i, l) closing the branch, l = i+4 .. j
-      if (on) {
-#pragma unroll 4
-        for (int l = i + 4 + r; l <= j; l += G) {
-          const double v = l == j ? qb : Qb[D(l - i, i)];
-          if (v != 0.0) m1 += v * T.mli * T.au[pair_raw(c[i], c[l])] * scp[j - l];
-        }
-      }
-      m1 = team_sum(m1, G);
-      if (on && r == 0) Qm1[D(d, i)] = m1;
-      double m = 0.0;  // Qm(i, j) = sum_u (sc^(u-i) + Qm(i, u-1)) Qm1(u, j)
-      if (on) {
-#pragma unroll 4
-        for (int u = i + r; u + 4 <= j; u += G)
-          m += (scp[u - i] + (u - 1 >= i ? Qm[D(u - 1 - i, i)] : 0.0)) * (u == i ? m1 : Qm1[D(j - u, u)]);
-      }
-      m = team_sum(m, G);
-      if (on && r == 0) Qm[D(d, i)] = m;
+      fold_qm_updates(w, T, M, i, j, r, G, on, qb);
     }
     __syncthreads();
   }
@@ -152,34 +124,11 @@ __global__ void __launch_bounds__(512) sk_fold_kernel(FoldLaunch P) {
 #endif
 
   // ---------------------------------------------------------------- exterior
-  if (tid == 0) Q5[0] = 1.0;
-  __syncthreads();
-  for (int j = 0; j < n; ++j) {
-    double s = 0.0;
-    for (int k = tid; k + 4 <= j; k += nt) {
-      const double v = Qb[D(j - k, k)];
-      if (v != 0.0) s += Q5[k] * v * T.au[pair_raw(c[k], c[j])];
-    }
-    s = block_sum(s, red);
-    if (tid == 0) Q5[j + 1] = Q5[j] * scp[1] + s;
-    __syncthreads();
-  }
-  const double Z = Q5[n];
+  const double Z = fold_q5_sweep(w, T, M, red);
   if (tid == 0 && P.log_z) P.log_z[blockIdx.x] = log(Z) - (double)n * P.log_sc;
   // the structure sampler (fold_sample.hip) walks Qb, Qm, Qm1 and Q5 only
   if (P.inside_only) return;
-  if (tid == 0) H5[n] = 1.0;
-  __syncthreads();
-  for (int k = n - 1; k >= 0; --k) {
-    double s = 0.0;
-    for (int j = k + 4 + tid; j < n; j += nt) {
-      const double v = Qb[D(j - k, k)];
-      if (v != 0.0) s += H5[j + 1] * v * T.au[pair_raw(c[k], c[j])];
-    }
-    s = block_sum(s, red);
-    if (tid == 0) H5[k] = H5[k + 1] * scp[1] + s;
-    __syncthreads();
-  }
+  fold_h5_sweep(w, T, M, red);
 #ifdef SK_FOLD_TIMING
   const uint64_t tk2 = clock64();
 #endif
@@ -195,65 +144,27 @@ __global__ void __launch_bounds__(512) sk_fold_kernel(FoldLaunch P) {
       const int i0 = base + tid / G, r = tid % G;
       const bool on = i0 < ncell;
       const int i = on ? i0 : 0, j = i + d;
-      // Hm(i,j): Qm(i,j2) += Qm(i,j) Qm1(j+1,j2);  Qb(i-1,j') ML rule with u = j
-      double hm = 0.0;
-      if (on) {
-#pragma unroll 4
-        for (int j2 = j + 5 + r; j2 < n; j2 += G) hm += Hm[D(j2 - i, i)] * Qm1[D(j2 - j - 1, j + 1)];
-        if (i >= 1) {
-          for (int jp = j + 6 + r; jp < n; jp += G) {
-            const double v = Hb[D(jp - i + 1, i - 1)];
-            if (v == 0.0) continue;
-            const int t1 = ptype(i - 1, jp);
-            if (!t1 || (ncg && is_gu(t1))) continue;
-            hm += v * T.mlc * T.au[t1] * scp[2] * Qm1[D(jp - j - 2, j + 1)];
-          }
-        }
-      }
-      hm = team_sum(hm, G);
-      if (on && r == 0) Hm[D(d, i)] = hm;
-      // Hm1(i,j): Qm(ii,j) += (sc^(i-ii) + Qm(ii,i-1)) Qm1(i,j), ii <= i;
-      //           Qb(i',j+1) ML rule with u + 1 = i
-      // (ii = i - e, e up: the threads read consecutive doubles)
-      double hm1 = 0.0;
-      if (on) {
-#pragma unroll 4
-        for (int e = r; e <= i; e += G) {
-          const double v = e == 0 ? hm : Hm[D(d + e, i - e)];
-          if (v != 0.0) hm1 += v * (scp[e] + (e >= 1 ? Qm[D(e - 1, i - e)] : 0.0));
-        }
-        if (j + 1 < n) {
-          for (int e = 6 + r; e <= i; e += G) {  // ip = i - e
-            const double v = Hb[D(d + 1 + e, i - e)];
-            if (v == 0.0) continue;
-            const int t1 = ptype(i - e, j + 1);
-            if (!t1 || (ncg && is_gu(t1))) continue;
-            hm1 += v * T.mlc * T.au[t1] * scp[2] * Qm[D(e - 2, i - e + 1)];
-          }
-        }
-      }
-      hm1 = team_sum(hm1, G);
-      if (on && r == 0) Hm1[D(d, i)] = hm1;
+      const double hm1 = fold_hm_updates(w, T, M, i, j, r, G, on);
       // Hb(i,j): exterior branch, Qm1(i,jj) += Qb(i,j) (branch) sc^(jj-j),
       //          enclosing interior loops (ip, jp) = (i-1-n1, j+1+n2):
       //          diagonal d+2+n1+n2
-      const int t = on ? ptype(i, j) : 0;
+      const int t = on ? M.ptype(i, j) : 0;
       double part = 0.0;
       if (t) {
         double s = r == 0 ? hm1 : 0.0;
 #pragma unroll 4
-        for (int jj = j + 1 + r; jj < n; jj += G) s += Hm1[D(jj - i, i)] * scp[jj - j];
+        for (int jj = j + 1 + r; jj < n; jj += G) s += w.hm1(jj - i, i) * scp[jj - j];
         part = s * T.mli * T.au[t];
         const int t2 = pair_raw(c[j], c[i]);
         for (int n1 = r; n1 <= min(30, i - 1); n1 += G) {
           const int ip = i - 1 - n1;
           const int n2m = min(30 - n1, n - 2 - j);
-          int sl = slot(d + 2 + n1);
+          int sl = fold_ring_slot(d + 2 + n1);
           for (int n2 = 0; n2 <= n2m; ++n2) {
-            const double v = RING ? ring[(size_t)sl * P.ring_n + ip] : Hb[D(d + 2 + n1 + n2, ip)];
-            sl = up(sl);
+            const double v = RING ? ring[(size_t)sl * P.max_n + ip] : w.hb(d + 2 + n1 + n2, ip);
+            sl = fold_ring_up(sl);
             if (v == 0.0) continue;
-            const int t1 = ptype(ip, j + 1 + n2);
+            const int t1 = M.ptype(ip, j + 1 + n2);
             if (!t1) continue;
             part += v * fold_interior(T, t1, t2, n1, n2, ncg) * scp[n1 + n2 + 2];
           }
@@ -261,11 +172,11 @@ __global__ void __launch_bounds__(512) sk_fold_kernel(FoldLaunch P) {
       }
       part = team_sum(part, G);
       if (on && r == 0) {
-        const double hb = t ? H5[j + 1] * Q5[i] * T.au[t] + part : 0.0;
-        const double qbij = Qb[D(d, i)];
-        Hb[D(d, i)] = hb;
-        if (RING) ring[(size_t)slot(d) * P.ring_n + i] = hb;
-        out[(size_t)i * n - (size_t)i * (i + 1) / 2 + (size_t)(j - i - 1)] = qbij != 0.0 ? qbij * hb / Z : 0.0;
+        const double hb = t ? w.h5()[j + 1] * w.q5()[i] * T.au[t] + part : 0.0;
+        const double qbij = w.qb(d, i);
+        w.hb(d, i) = hb;
+        if (RING) ring[(size_t)fold_ring_slot(d) * P.max_n + i] = hb;
+        out[tri_index(n, i, j)] = qbij != 0.0 ? qbij * hb / Z : 0.0;
       }
     }
     __syncthreads();
@@ -291,24 +202,16 @@ size_t fold_lds_bytes(const FoldLaunch& P, int max_n) {
 
 bool fold_ring(int max_n) { return max_n <= kFoldRingMaxN; }
 
-template <bool RING, bool GTAB>
-static hipError_t launch_fold_t(const FoldLaunch& P, int n_seqs, size_t lds, hipStream_t st) {
-  hipError_t e = hipFuncSetAttribute((const void*)sk_fold_kernel<RING, GTAB>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((sk_fold_kernel<RING, GTAB>), dim3(n_seqs), dim3(512), lds, st, P);
-  return hipGetLastError();
-}
-
 hipError_t launch_fold(const FoldLaunch& P0, int n_seqs, int max_n, hipStream_t st) {
   if (n_seqs <= 0) return hipSuccess;
   FoldLaunch P = P0;
-  P.ring_n = fold_ring(max_n) ? max_n : 0;
+  P.max_n = max_n;
   const size_t lds = fold_lds_bytes(P, max_n);
   if (lds > kFoldLdsMax) return hipErrorInvalidValue;
-  if (fold_ring(max_n)) return launch_fold_t<true, false>(P, n_seqs, lds, st);  // (tables always fit)
-  return fold_gtab(P, max_n) ? launch_fold_t<false, true>(P, n_seqs, lds, st)
-                             : launch_fold_t<false, false>(P, n_seqs, lds, st);
+  const bool ring = fold_ring(max_n);  // (its tables always fit)
+  return launch_fold_kernel(ring ? sk_fold_kernel<true, false>
+                                 : fold_gtab(P, max_n) ? sk_fold_kernel<false, true> : sk_fold_kernel<false, false>,
+                            P, dim3(n_seqs), 512, lds, st);
 }
 
 }  // namespace sk

@@ -4,9 +4,10 @@
 //
 // Runs after an inside_only launch of the fold kernel (fold.hip), which
 // leaves the inside tables Qb, Qm, Qm1 (by diagonal) and the exterior prefix
-// Q5 in the work buffer.  A structure is drawn by walking those tables top
-// down: an open segment is one cell of one table, and the candidates of its
-// decision are exactly the terms of the inside sum that produced the cell,
+// Q5 in the work buffer (FoldWork, launch.h; the pair types, loop factors
+// and launch wrapper shared with the fold: fold_dev.h).  A structure is drawn
+// by walking those tables top down: an open segment is one cell of one
+// table, and the candidates of its decision are exactly the terms of the inside sum that produced the cell,
 // with the same pair types, loop factors and scale powers -- so a structure
 // comes out with probability exp(-E/kT) / Z whatever the per-nucleotide
 // scale is.
@@ -94,12 +95,13 @@ __global__ void __launch_bounds__(kSampleWaves * 64) sk_fold_sample_kernel(FoldS
   const int n = sq.n;
   const int tid = threadIdx.x, nt = blockDim.x;
   const int lane = tid & 63, wave = tid >> 6;
-  const size_t N2 = (size_t)n * n;
-  const double* W = P.work + sq.work_off;
-  const double *Qb = W, *Qm = W + N2, *Qm1 = W + 2 * N2, *Q5 = W + 6 * N2;
+  // (the tables' bases taken once: with FoldWork's accessors in every
+  // candidate, or the shared table views, the walks measured 0.9 % slower)
+  const FoldWork w{P.work + sq.work_off, (size_t)n, kFoldTables};
+  const double *Qb = &w.qb(0, 0), *Qm = &w.qm(0, 0), *Qm1 = &w.qm1(0, 0), *Q5 = w.q5();
   // LDS: the Boltzmann tables, a stack of open segments per wave, the codes
   double* tl = ssm;
-  const int cap = fold_sample_stack_cap(P.ring_n);  // ring_n: the launch's longest sequence
+  const int cap = fold_sample_stack_cap(P.max_n);
   int2* stack = reinterpret_cast<int2*>(tl + P.n_tab_pad) + (size_t)wave * cap;
   int8_t* c = reinterpret_cast<int8_t*>(reinterpret_cast<int2*>(tl + P.n_tab_pad) + (size_t)kSampleWaves * cap);
   for (int k = tid; k < P.n_tab; k += nt) tl[k] = P.tab[k];
@@ -256,18 +258,14 @@ size_t fold_sample_lds_bytes(const FoldLaunch& P, int max_n) {
 hipError_t launch_fold_sample(const FoldSampleLaunch& S0, int n_seqs, int max_n, hipStream_t st) {
   if (n_seqs <= 0 || S0.n_samples <= 0) return hipSuccess;
   FoldSampleLaunch S = S0;
-  S.F.ring_n = max_n;  // (the sampler reads no ring: the stack's row length)
+  S.F.max_n = max_n;
   const size_t lds = fold_sample_lds_bytes(S.F, max_n);
   if (lds > kFoldLdsMax) return hipErrorInvalidValue;
-  hipError_t e = hipFuncSetAttribute((const void*)sk_fold_sample_kernel,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return e;
   // enough workgroups to fill the chip when the call has few sequences
   const int per_wg = (S.n_samples + kSampleWaves - 1) / kSampleWaves;
   int gy = (2048 + n_seqs - 1) / n_seqs;
   gy = gy < 1 ? 1 : (gy > per_wg ? per_wg : gy);
-  hipLaunchKernelGGL(sk_fold_sample_kernel, dim3(n_seqs, gy), dim3(kSampleWaves * 64), lds, st, S);
-  return hipGetLastError();
+  return launch_fold_kernel(sk_fold_sample_kernel, S, dim3(n_seqs, gy), kSampleWaves * 64, lds, st);
 }
 
 }  // namespace sk

@@ -6,6 +6,7 @@
 #include <cstdint>
 
 #include "device_set.h"
+#include "tri_index.h"
 
 namespace sk {
 
@@ -275,17 +276,19 @@ struct PhmmLaunch {
 size_t phmm_pair_bytes(int n1, int m1);
 hipError_t launch_phmm(const PhmmLaunch& P, hipStream_t st);
 
-// McCaskill fold (fold.hip): one workgroup per sequence
+// The folds (fold.hip, fold_ali.hip, fold_sample.hip; shared device code in
+// fold_dev.h).  One item of a launch: a sequence, or an alignment of n_rows
+// rows; one workgroup per item.
 struct FoldSeq {
-  int64_t seq_off = 0;   // into codes
-  int64_t work_off = 0;  // into work: 10 n^2 + 2 (n + 1) doubles
+  int64_t seq_off = 0;   // into codes: the first code of the first row (n_rows rows of n codes)
+  int64_t work_off = 0;  // into work: FoldWork::doubles of the launch's table count
   int64_t out_off = 0;   // into out: n (n - 1) / 2 packed probabilities
   int64_t lp_off = 0;    // into lp (--noLonelyPairs): n x n pair filter
-  int32_t n = 0, pad = 0;
+  int32_t n = 0, n_rows = 1;
 };
 struct FoldLaunch {
   const FoldSeq* seqs = nullptr;
-  const int8_t* codes = nullptr;  // A C G U = 0..3, anything else -1
+  const int8_t* codes = nullptr;  // A C G U = 0..3, anything else (a blank of an alignment) -1
   const double* tab = nullptr;    // Boltzmann factors, offsets below (host: fold_tables)
   int32_t o_st = 0, o_hp = 0, o_bu = 0, o_in = 0, o_ni = 0, o_au = 0, o_ml = 0, o_scp = 0;
   double log_sc = 0.0;            // ln of the per-nucleotide scale
@@ -293,14 +296,42 @@ struct FoldLaunch {
   const uint8_t* lp = nullptr;    // --noLonelyPairs pair filter (nullptr: off)
   int32_t n_tab = 0, n_tab_pad = 0;  // table length (doubles), rounded up to 2 (LDS copy)
   int32_t n_small = 0;              // the fixed-size head of the tables (o_st .. o_ml)
-  int32_t ring_n = 0;               // set by launch_fold: ring row length (0: no ring)
-  double* work = nullptr;           // per sequence 6 n^2 + 2 (n + 1) doubles (fold_work_doubles)
+  int32_t max_n = 0;                // set by the launch functions: the launch's longest item (the row
+                                    // length of the LDS ring, the capacity of the sampler's stacks)
+  double* work = nullptr;           // per item a FoldWork
   double* out = nullptr;
-  double* log_z = nullptr;        // per sequence of the launch (nullptr: not wanted)
-  int32_t inside_only = 0;        // stop after the inside pass and Q5 (the sampler's input)
+  double* log_z = nullptr;        // per item of the launch (nullptr: not wanted)
+  int32_t inside_only = 0;        // fold.hip: stop after the inside pass and Q5 (the sampler's input)
+  int32_t o_ali = 0;              // fold_ali.hip, in tab: the row energies (host: fold_tables_ali)
 };
-// the fold kernel keeps the interior-loop window of the inside / outside
-// tables in LDS for sequences up to this length (33 n doubles)
+
+// Work buffer of one item: `tables` n x n tables by diagonal (cell (i, i+d)
+// at d n + i), then the exterior prefix Q5 and its adjoint H5, n + 1 each.
+// Every fold's passes run over the first six; the consensus fold keeps its
+// four per-cell tables behind them.
+constexpr int kFoldTables = 6, kFoldAliTables = 10;
+struct FoldWork {
+  double* base;
+  size_t n;
+  int tables;
+  __host__ __device__ static size_t doubles(int tables, size_t n) { return (size_t)tables * n * n + 2 * (n + 1); }
+  // cell (i, i + d) of table k
+  __host__ __device__ double& at(int k, int d, int i) const { return (base + (size_t)k * n * n)[(size_t)d * n + i]; }
+  __host__ __device__ double& qb(int d, int i) const { return at(0, d, i); }   // inside: pair closes a loop
+  __host__ __device__ double& qm(int d, int i) const { return at(1, d, i); }   // >= 1 multiloop branch
+  __host__ __device__ double& qm1(int d, int i) const { return at(2, d, i); }  // one branch starting at i
+  __host__ __device__ double& hb(int d, int i) const { return at(3, d, i); }   // their adjoints
+  __host__ __device__ double& hm(int d, int i) const { return at(4, d, i); }
+  __host__ __device__ double& hm1(int d, int i) const { return at(5, d, i); }
+  __host__ __device__ double& cell(int k, int d, int i) const { return at(kFoldTables + k, d, i); }  // per-cell table k
+  __host__ __device__ double* q5() const { return base + (size_t)tables * n * n; }
+  __host__ __device__ double* h5() const { return q5() + n + 1; }
+};
+inline size_t fold_work_doubles(size_t n) { return FoldWork::doubles(kFoldTables, n); }
+inline size_t fold_ali_work_doubles(size_t n) { return FoldWork::doubles(kFoldAliTables, n); }
+
+// the fold kernels keep the interior-loop window of the inside / outside
+// tables in LDS for items up to this length (33 n doubles)
 constexpr int kFoldRingMaxN = 248;
 // dynamic LDS a fold launch may take (160 KB less the kernel's static block sums)
 constexpr size_t kFoldLdsMax = 163840 - 256;
@@ -309,7 +340,6 @@ bool fold_ring(int max_n);
 // and codes would not fit the LDS)
 bool fold_gtab(const FoldLaunch& P, int max_n);
 size_t fold_lds_bytes(const FoldLaunch& P, int max_n);
-inline size_t fold_work_doubles(size_t n) { return 6 * n * n + 2 * (n + 1); }
 hipError_t launch_fold(const FoldLaunch& P, int n_seqs, int max_n, hipStream_t st);
 
 // Stochastic structure sampling (fold_sample.hip): walks the inside tables an
@@ -330,25 +360,10 @@ constexpr int32_t kFoldSampleStack = 3;     // more open segments than n / 2 + 4
 size_t fold_sample_lds_bytes(const FoldLaunch& P, int max_n);
 hipError_t launch_fold_sample(const FoldSampleLaunch& P, int n_seqs, int max_n, hipStream_t st);
 
-// Consensus fold of alignments (fold_ali.hip): one workgroup per alignment,
-// the fold's passes over per-cell tables a first phase fills from the rows
-struct FoldAliSeq {
-  int64_t row_off = 0;   // into codes: n_rows rows of n codes
-  int64_t work_off = 0;  // into F.work: fold_ali_work_doubles(n)
-  int64_t out_off = 0;   // into F.out: n (n - 1) / 2 packed probabilities
-  int64_t lp_off = 0;    // into F.lp (--noLonelyPairs): n x n filter over the allowed column pairs
-  int32_t n = 0, n_rows = 0;
-};
-struct FoldAliLaunch {
-  FoldLaunch F;  // tab and its offsets, log_sc, no_gu, lp, work, out, log_z (seqs and codes unused)
-  const FoldAliSeq* alns = nullptr;
-  const int8_t* codes = nullptr;  // A C G U = 0..3, blank -1
-  int32_t o_ali = 0;              // in F.tab: 8 x 8 stack energies by energy type, then kT, TerminalAU, bulge(1)
-};
-constexpr int kFoldAliTabExtra = 64 + 3;
-size_t fold_ali_lds_bytes(const FoldLaunch& F, int max_n);
-inline size_t fold_ali_work_doubles(size_t n) { return 10 * n * n + 2 * (n + 1); }
-hipError_t launch_fold_ali(const FoldAliLaunch& P, int n_alns, int max_n, hipStream_t st);
+// Consensus fold of alignments (fold_ali.hip): the fold's passes over
+// per-cell tables a first phase fills from the rows (FoldLaunch::o_ali)
+size_t fold_ali_lds_bytes(const FoldLaunch& P, int max_n);
+hipError_t launch_fold_ali(const FoldLaunch& P, int n_alns, int max_n, hipStream_t st);
 
 enum CombineMode : int32_t {
   kCombineStem = 0,      // K = stem

@@ -27,7 +27,7 @@
 #include <vector>
 
 #include "../../include/stem_kernel.h"
-#include "host/fold_params.h"
+#include "host/fold_host.h"
 #include "kernels/fold_ali_model.h"
 #include "kernels/fold_rng.h"
 #include "host/sk_internal.h"
@@ -4061,100 +4061,32 @@ int sk_fold_synthetic(const char* seq, int32_t n, int32_t no_gu, double* out) {
   return SK_OK;
 }
 
-// ---------------------------------------------------------------- McCaskill fold (f1)
+// ---------------------------------------------------------------- the GPU folds (f1)
+// McCaskill fold, structure sampling and the consensus fold of alignments go
+// through one batch driver (fold_batches); host pieces: host/fold_host.cpp.
 namespace {
 
-// Boltzmann factor tables of fold.hip (host/fold_params.h), laid out in one
-// buffer: the fixed-size tables first (o_st .. o_ml, n_small doubles), then
-// the two whose length follows the batch's longest sequence max_len (hairpin,
-// scale powers), so a launch whose tables outgrow the LDS keeps the first
-// part in LDS and reads the tail from HBM (fold.hip GTAB).  Entry k of every
-// table is the same double whatever max_len is.
-void fold_tables(int max_len, sk::FoldLaunch& L, std::vector<double>& t) {
-  using namespace sk::foldp;
-  t.clear();
-  auto bz = [](double e) { return std::exp(-e / kT); };
-  L.o_st = (int32_t)t.size();
-  for (int a = 0; a < 7; ++a)
-    for (int b = 0; b < 7; ++b) t.push_back(a && b ? bz(stack37[a][b]) : 0.0);
-  L.o_bu = (int32_t)t.size();
-  for (int k = 0; k <= max_loop; ++k) t.push_back(k ? bz(bulge37[k]) : 0.0);
-  L.o_in = (int32_t)t.size();
-  for (int k = 0; k <= max_loop; ++k) t.push_back(k >= 2 ? bz(interior37[k]) : 0.0);
-  L.o_ni = (int32_t)t.size();
-  for (int k = 0; k <= max_loop; ++k) t.push_back(bz(std::min(max_ninio, ninio * k)));
-  L.o_au = (int32_t)t.size();
-  for (int k = 0; k < 7; ++k) t.push_back(k > 2 ? bz(terminal_au) : 1.0);
-  L.o_ml = (int32_t)t.size();
-  t.push_back(bz(ml_closing + ml_intern));
-  t.push_back(bz(ml_intern));
-  L.n_small = (int32_t)t.size();
-  L.o_hp = (int32_t)t.size();
-  for (int k = 0; k <= max_len + 1; ++k) {
-    if (k < 3) {
-      t.push_back(0.0);
-      continue;
-    }
-    double e = hairpin37[k <= 30 ? k : 30];
-    if (k > 30) e += lxc * std::log((double)k / 30.0);
-    t.push_back(bz(e));
-  }
-  L.o_scp = (int32_t)t.size();
-  for (int k = 0; k <= max_len + 2; ++k) t.push_back(std::exp(log_sc * k));
-  L.log_sc = log_sc;
-  L.n_tab = (int32_t)t.size();
-  L.n_tab_pad = (L.n_tab + 1) & ~1;
-}
+// What the single-sequence fold and the consensus fold give the driver
+struct FoldKind {
+  int tables;                                              // n x n work tables per item
+  double (*more_bytes)(double n, double rows, bool no_lp);  // an item's share of the memory budget besides them
+  void (*lonely)(const int8_t* c, int n_rows, int n, bool no_gu, uint8_t* lp);  // --noLonelyPairs filter of an item
+  void (*more_tables)(sk::FoldLaunch&, std::vector<double>&);                   // after fold_tables (nullptr: none)
+  size_t (*lds_bytes)(const sk::FoldLaunch&, int);
+  hipError_t (*launch)(const sk::FoldLaunch&, int, int, hipStream_t);
+  const char *too_long, *out_of_range;  // the wording of its errors
+};
+const FoldKind kFoldPlain = {
+    sk::kFoldTables, [](double, double, bool) { return 0.0; },
+    [](const int8_t* c, int, int n, bool no_gu, uint8_t* lp) { sk::lonely_pair_table(c, n, no_gu, lp); }, nullptr,
+    sk::fold_lds_bytes, sk::launch_fold, "fold: sequence too long for the fold kernel's LDS",
+    "fold: partition function out of double range (sequence too long)"};
+const FoldKind kFoldAli = {
+    sk::kFoldAliTables, [](double n, double rows, bool no_lp) { return n * rows + (no_lp ? n * n : 0.0); },
+    sk::lonely_pair_table_ali, sk::fold_tables_ali, sk::fold_ali_lds_bytes, sk::launch_fold_ali,
+    "consensus fold: alignment too long for the kernel's LDS",
+    "consensus fold: partition function out of double range (alignment too long)"};
 
-int8_t fold_code(char ch) {
-  switch (ch) {
-    case 'A': case 'a': return 0;
-    case 'C': case 'c': return 1;
-    case 'G': case 'g': return 2;
-    case 'U': case 'u': case 'T': case 't': return 3;
-    default: return -1;
-  }
-}
-
-}  // namespace
-
-// --noLonelyPairs (common/bpmatrix.cpp:56-58, 149, Vienna::noLonelyPairs):
-// the legacy ViennaRNA partition function applies it through its pair-type
-// table only (1.8 part_func.c make_ptypes; not vendored).  Walking each chain
-// (i, j), (i-1, j+1), ... outward from its innermost pair (j - i = 4 or 5),
-// a pair is dropped when its inner neighbour was dropped or cannot pair and
-// its outer neighbour cannot pair; the outer type is re-read only inside the
-// sequence, so a chain's outermost pair compares against its own type.
-// lp[i*n + j] = 1 where the pair survives (codes: fold_code, -1 never pairs).
-// (can(i, j): whether the pair can form at all; the consensus fold walks its
-// allowed column pairs)
-extern "C++" template <class Can>
-static void lonely_pair_walk(int n, Can can, uint8_t* lp) {
-  std::fill(lp, lp + (size_t)n * n, (uint8_t)0);
-  for (int k = 0; k < n; ++k)
-    for (int l = 1; l <= 2; ++l) {
-      int i = k, j = k + 3 + l, otype = 0, ntype = 0;
-      if (j >= n) continue;
-      int type = can(i, j);
-      for (; i >= 0 && j < n; --i, ++j) {
-        if (i > 0 && j < n - 1) ntype = can(i - 1, j + 1);
-        if (!otype && !ntype) type = 0;
-        lp[(size_t)i * n + j] = type != 0;
-        otype = type;
-        type = ntype;
-      }
-    }
-}
-
-void lonely_pair_table(const int8_t* c, int n, bool no_gu, uint8_t* lp) {
-  static const int8_t pt[16] = {0, 0, 0, 5, 0, 0, 1, 0, 0, 2, 0, 4, 6, 0, 3, 0};
-  lonely_pair_walk(n, [&](int i, int j) {
-    const int t = (c[i] < 0 || c[j] < 0) ? 0 : pt[c[i] * 4 + c[j]];
-    return (no_gu && (t == 3 || t == 4)) ? 0 : (int)t;
-  }, lp);
-}
-
-namespace {
 // what sk_fold_sample adds to a fold call: after the inside pass of each
 // batch, n_samples structures per sequence are drawn on the same stream
 struct FoldSampling {
@@ -4163,92 +4095,77 @@ struct FoldSampling {
   char* structs = nullptr;  // optional, sk_fold_sample's out_structs
 };
 
-// Batches of the fold calls (sk_fold_mccaskill, sk_fold_sample,
-// sk_fold_alignment): the device memory one batch's tables may take ...
-int fold_budget(sk_context* ctx, double* budget) {
-  size_t free_b = 0, total_b = 0;
-  SK_HIP(ctx, hipMemGetInfo(&free_b, &total_b));
-  *budget = std::min(16e9, 0.4 * (double)free_b);
-  return SK_OK;
-}
-// ... and the end of the batch that starts at item b0: the items whose bytes
-// (bytes(k)) fit the budget together, at least one
-extern "C++" template <class Bytes>
-int32_t fold_batch_end(int32_t b0, int32_t n, double budget, Bytes bytes) {
-  double sum = 0.0;
-  int32_t b1 = b0;
-  for (; b1 < n; ++b1) {
-    const double w = bytes(b1);
-    if (b1 > b0 && sum + w > budget) break;
-    sum += w;
+// n items, item k of n_rows[k] rows (nullptr: one each) of equal length, the
+// items' rows back to back in rows, in batches whose tables fit the memory
+// budget: out gets the probabilities (sm: optional, count / n_samples)
+int fold_batches(sk_context* ctx, const FoldKind& K, int32_t n, const int32_t* n_rows, const char* const* rows,
+                 int32_t flags, double* out, double* log_z, const FoldSampling* sm) {
+  if (n == 0) return SK_OK;
+  std::vector<int> len(n);
+  for (size_t k = 0, r = 0; k < (size_t)n; r += n_rows ? n_rows[k] : 1, ++k) {
+    if (!rows[r]) return fail(ctx, SK_ERR_INVALID, "null sequence");
+    len[k] = (int)std::strlen(rows[r]);
   }
-  return b1;
-}
-
-// sk_fold_mccaskill (sm == nullptr: out gets the McCaskill probabilities) and
-// sk_fold_sample (out, optional, gets count / n_samples): the batches, their
-// buffers and the fold launch are the same
-int fold_run(sk_context* ctx, int32_t n, const char* const* seqs, int32_t flags, double* out,
-             double* log_z, const FoldSampling* sm) {
   const bool no_lp = (flags & SK_FOLD_NO_LONELY_PAIRS) != 0;
   const size_t ns = sm ? (size_t)sm->n_samples : 0;
   const bool want_str = sm && sm->structs;
-  if (n == 0) return SK_OK;
-  std::vector<int> len(n);
-  int max_len = 0;
-  for (int32_t k = 0; k < n; ++k) {
-    if (!seqs[k]) return fail(ctx, SK_ERR_INVALID, "null sequence");
-    len[k] = (int)std::strlen(seqs[k]);
-    max_len = std::max(max_len, len[k]);
-  }
   sk::FoldLaunch L;
   std::vector<double> tab;
   L.no_gu = (flags & SK_FOLD_NO_GU) ? 1 : 0;
   L.no_closing_gu = (flags & SK_FOLD_NO_CLOSING_GU) ? 1 : 0;
-  double budget = 0.0;
-  if (int rc = fold_budget(ctx, &budget)) return rc;
+  L.inside_only = sm ? 1 : 0;
+  // the device memory one batch's tables may take (experiments build:
+  // SK_FOLD_BUDGET gives it in bytes, so a test can split a small call)
+  size_t free_b = 0, total_b = 0;
+  SK_HIP(ctx, hipMemGetInfo(&free_b, &total_b));
+  double budget = std::min(16e9, 0.4 * (double)free_b);
+  if (const char* e = SK_KNOB("SK_FOLD_BUDGET")) budget = std::atof(e);
   hipStream_t S = ctx->stream;
-  size_t out_host = 0;  // packed output offset of sequence k (host)
+  size_t out_host = 0;  // packed outputs of the batches before (host)
   size_t str_host = 0;  // sampled structures written so far (host)
-  for (int32_t b0 = 0; b0 < n;) {
-    // batch: sequences whose tables fit the budget (at least one)
+  size_t row = 0;       // first row of item b0 in rows
+  int n_batches = 0;
+  for (int32_t b0 = 0; b0 < n; ++n_batches) {
+    // (the sampled structures of the batch count too: n_samples chars per nucleotide)
+    const int32_t b1 = sk::fold_batch_end(b0, n, budget, [&](int32_t k) {
+      return (double)sk::FoldWork::doubles(K.tables, (size_t)len[k]) * 8.0 +
+             K.more_bytes((double)len[k], n_rows ? (double)n_rows[k] : 1.0, no_lp) +
+             (want_str ? (double)len[k] * (double)ns : 0.0);
+    });
     std::vector<sk::FoldSeq> sq;
     std::vector<int8_t> codes;
     std::vector<uint8_t> lp;  // --noLonelyPairs tables
     size_t work = 0, outn = 0;
-    // (the sampled structures of the batch count too: n_samples chars per nucleotide)
-    const int32_t b1 = fold_batch_end(b0, n, budget, [&](int32_t k) {
-      return (double)sk::fold_work_doubles((size_t)len[k]) * 8.0 + (want_str ? (double)len[k] * (double)ns : 0.0);
-    });
     int bmax = 0;
     for (int32_t k = b0; k < b1; ++k) {
       const size_t nn = (size_t)len[k];
-      const size_t w = sk::fold_work_doubles(nn);
       sk::FoldSeq f;
       f.seq_off = (int64_t)codes.size();
       f.work_off = (int64_t)work;
       f.out_off = (int64_t)outn;
       f.n = (int32_t)nn;
-      for (size_t a = 0; a < nn; ++a) codes.push_back(fold_code(seqs[k][a]));
+      f.n_rows = n_rows ? n_rows[k] : 1;
+      codes.resize(codes.size() + (size_t)f.n_rows * nn);
+      for (int32_t r = 0; r < f.n_rows; ++r, ++row) sk::fold_codes(rows[row], nn, codes.data() + f.seq_off + r * nn);
       if (no_lp) {
         f.lp_off = (int64_t)lp.size();
         lp.resize(lp.size() + nn * nn);
-        lonely_pair_table(codes.data() + f.seq_off, (int)nn, L.no_gu != 0, lp.data() + f.lp_off);
+        K.lonely(codes.data() + f.seq_off, f.n_rows, (int)nn, L.no_gu != 0, lp.data() + f.lp_off);
       }
-      work += w;
+      work += sk::FoldWork::doubles(K.tables, nn);
       outn += nn > 1 ? nn * (nn - 1) / 2 : 0;
       bmax = std::max(bmax, (int)nn);
       sq.push_back(f);
     }
     const int nb = b1 - b0;
-    fold_tables(bmax, L, tab);  // sized by this batch's longest sequence
-    if (sk::fold_lds_bytes(L, bmax) > sk::kFoldLdsMax)
-      return fail(ctx, SK_ERR_UNSUPPORTED, "fold: sequence too long for the fold kernel's LDS");
+    sk::fold_tables(bmax, L, tab);  // sized by this batch's longest item
+    if (K.more_tables) K.more_tables(L, tab);
+    if (K.lds_bytes(L, bmax) > sk::kFoldLdsMax) return fail(ctx, SK_ERR_UNSUPPORTED, K.too_long);
     if (sm && sk::fold_sample_lds_bytes(L, bmax) > sk::kFoldLdsMax)
       return fail(ctx, SK_ERR_UNSUPPORTED, "fold: sequence too long for the sampling kernel's LDS");
     const size_t strn = want_str ? codes.size() * ns : 0;  // sampled structures, chars
-    size_t need = sq.size() * sizeof(sk::FoldSeq) + codes.size() + lp.size() + tab.size() * 8 +
-                  (outn + nb) * 8 + strn + 10 * 256;
+    const size_t need = sq.size() * sizeof(sk::FoldSeq) + codes.size() + lp.size() + tab.size() * 8 +
+                        (outn + nb) * 8 + strn + 10 * 256;
     int rc = ensure_work(ctx, need);
     if (rc) return rc;
     rc = ensure_scratch(ctx, std::max<size_t>(work * 8, 64));
@@ -4262,7 +4179,6 @@ int fold_run(sk_context* ctx, int32_t n, const char* const* seqs, int32_t flags,
     uint8_t* d_lp = no_lp ? A.take<uint8_t>(std::max<size_t>(lp.size(), 1)) : nullptr;
     if (no_lp && !lp.empty())
       SK_HIP(ctx, hipMemcpyAsync(d_lp, lp.data(), lp.size(), hipMemcpyHostToDevice, S));
-    L.lp = d_lp;
     SK_HIP(ctx, hipMemcpyAsync(d_sq, sq.data(), sq.size() * sizeof(sk::FoldSeq), hipMemcpyHostToDevice, S));
     if (!codes.empty())
       SK_HIP(ctx, hipMemcpyAsync(d_codes, codes.data(), codes.size(), hipMemcpyHostToDevice, S));
@@ -4274,14 +4190,14 @@ int fold_run(sk_context* ctx, int32_t n, const char* const* seqs, int32_t flags,
     int32_t* d_status = sm ? A.take<int32_t>(1) : nullptr;
     if (want_str && strn) SK_HIP(ctx, hipMemsetAsync(d_str, '.', strn, S));
     if (sm) SK_HIP(ctx, hipMemsetAsync(d_status, 0, sizeof(int32_t), S));
-    L.inside_only = sm ? 1 : 0;
     L.seqs = d_sq;
     L.codes = d_codes;
     L.tab = d_tab;
+    L.lp = d_lp;
     L.work = ctx->scratch;
     L.out = d_out;
     L.log_z = d_lz;
-    SK_HIP(ctx, sk::launch_fold(L, nb, bmax, S));
+    SK_HIP(ctx, K.launch(L, nb, bmax, S));
     std::vector<double> lz(nb);
     std::vector<uint32_t> cnt;
     int32_t status = 0;
@@ -4307,8 +4223,7 @@ int fold_run(sk_context* ctx, int32_t n, const char* const* seqs, int32_t flags,
     SK_HIP(ctx, hipMemcpyAsync(lz.data(), d_lz, nb * 8, hipMemcpyDeviceToHost, S));
     SK_HIP(ctx, hipStreamSynchronize(S));
     for (int k = 0; k < nb; ++k) {
-      if (!std::isfinite(lz[k]))
-        return fail(ctx, SK_ERR_UNSUPPORTED, "fold: partition function out of double range (sequence too long)");
+      if (!std::isfinite(lz[k])) return fail(ctx, SK_ERR_UNSUPPORTED, K.out_of_range);
       if (log_z) log_z[b0 + k] = lz[k];
     }
     if (status == sk::kFoldSampleRunaway)
@@ -4322,8 +4237,10 @@ int fold_run(sk_context* ctx, int32_t n, const char* const* seqs, int32_t flags,
     str_host += strn;
     b0 = b1;
   }
+  if (std::getenv("SK_HOST_STATS")) std::fprintf(stderr, "[sk] fold: %d items in %d batches\n", (int)n, n_batches);
   return SK_OK;
 }
+
 }  // namespace
 
 int sk_fold_mccaskill(sk_context* ctx, int32_t n, const char* const* seqs, int32_t flags,
@@ -4331,7 +4248,7 @@ int sk_fold_mccaskill(sk_context* ctx, int32_t n, const char* const* seqs, int32
   if (!ctx || n < 0 || (n > 0 && (!seqs || !out))) return fail(ctx, SK_ERR_INVALID, "null argument");
   if (flags & ~(SK_FOLD_NO_GU | SK_FOLD_NO_CLOSING_GU | SK_FOLD_NO_LONELY_PAIRS))
     return fail(ctx, SK_ERR_UNSUPPORTED, "fold: unknown flag");
-  return fold_run(ctx, n, seqs, flags, out, log_z, nullptr);
+  return fold_batches(ctx, kFoldPlain, n, nullptr, seqs, flags, out, log_z, nullptr);
 }
 
 int sk_fold_sample(sk_context* ctx, int32_t n, const char* const* seqs, int32_t flags,
@@ -4345,29 +4262,12 @@ int sk_fold_sample(sk_context* ctx, int32_t n, const char* const* seqs, int32_t 
   sm.n_samples = n_samples;
   sm.seed = seed;
   sm.structs = out_structs;
-  return fold_run(ctx, n, seqs, flags, out_bpp, log_z, &sm);
+  return fold_batches(ctx, kFoldPlain, n, nullptr, seqs, flags, out_bpp, log_z, &sm);
 }
 
 double sk_fold_sample_uniform(uint64_t seed, int32_t seq, int32_t sample, int32_t draw) {
   return sk::rng_uniform(sk::rng_stream(seed, seq, sample), draw);
 }
-
-// ---------------------------------------------------------------- consensus fold
-namespace {
-// --noLonelyPairs of the consensus fold: lonely_pair_table's walk over the
-// column pairs the covariance score allows (c: n_rows rows of n codes)
-void lonely_pair_table_ali(const int8_t* c, int n_rows, int n, bool no_gu, uint8_t* lp) {
-  std::vector<uint8_t> ok((size_t)n * n, 0);
-  for (int i = 0; i < n; ++i)
-    for (int j = i + 4; j < n; ++j) {
-      sk::AliCounts pf;
-      for (int s = 0; s < n_rows; ++s) pf.add(sk::ali_row_type(c[(size_t)s * n + i], c[(size_t)s * n + j], no_gu));
-      int64_t ps = 0;
-      ok[(size_t)i * n + j] = sk::ali_allowed(pf, n_rows, j - i, &ps);
-    }
-  lonely_pair_walk(n, [&](int i, int j) { return (int)ok[(size_t)i * n + j]; }, lp);
-}
-}  // namespace
 
 int sk_fold_alignment(sk_context* ctx, int32_t n_aln, const int32_t* n_rows, const char* const* rows,
                       int32_t flags, double* out, double* log_z) {
@@ -4377,114 +4277,18 @@ int sk_fold_alignment(sk_context* ctx, int32_t n_aln, const int32_t* n_rows, con
   if (flags & SK_FOLD_NO_CLOSING_GU)
     return fail(ctx, SK_ERR_UNSUPPORTED,
                 "consensus fold: --noClosingGU has no per-column meaning when the rows differ");
-  if (n_aln == 0) return SK_OK;
-  const bool no_lp = (flags & SK_FOLD_NO_LONELY_PAIRS) != 0;
-  std::vector<int> len(n_aln);
-  std::vector<size_t> first(n_aln + 1, 0);  // first row of alignment k in rows
-  for (int32_t k = 0; k < n_aln; ++k) {
+  size_t r = 0;  // row in rows
+  for (int32_t k = 0, len = 0; k < n_aln; ++k) {
     if (n_rows[k] < 1) return fail(ctx, SK_ERR_INVALID, "consensus fold: an alignment needs at least one row");
     if (n_rows[k] > sk::kAliMaxRows) return fail(ctx, SK_ERR_UNSUPPORTED, "consensus fold: too many rows");
-    first[k + 1] = first[k] + (size_t)n_rows[k];
-    for (size_t r = first[k]; r < first[k + 1]; ++r) {
+    for (int32_t a = 0; a < n_rows[k]; ++a, ++r) {
       if (!rows[r]) return fail(ctx, SK_ERR_INVALID, "null row");
       const int m = (int)std::strlen(rows[r]);
-      if (r == first[k]) len[k] = m;
-      else if (m != len[k]) return fail(ctx, SK_ERR_INVALID, "consensus fold: rows of unequal length");
+      if (a == 0) len = m;
+      else if (m != len) return fail(ctx, SK_ERR_INVALID, "consensus fold: rows of unequal length");
     }
   }
-  sk::FoldAliLaunch L;
-  std::vector<double> tab;
-  L.F.no_gu = (flags & SK_FOLD_NO_GU) ? 1 : 0;
-  double budget = 0.0;
-  if (int rc = fold_budget(ctx, &budget)) return rc;
-  hipStream_t S = ctx->stream;
-  size_t out_host = 0;
-  for (int32_t b0 = 0; b0 < n_aln;) {
-    const int32_t b1 = fold_batch_end(b0, n_aln, budget, [&](int32_t k) {
-      const double nn = (double)len[k];
-      return (double)sk::fold_ali_work_doubles((size_t)len[k]) * 8.0 + nn * (double)n_rows[k] + (no_lp ? nn * nn : 0.0);
-    });
-    std::vector<sk::FoldAliSeq> sq;
-    std::vector<int8_t> codes;
-    std::vector<uint8_t> lp;
-    size_t work = 0, outn = 0;
-    int bmax = 0;
-    for (int32_t k = b0; k < b1; ++k) {
-      const size_t nn = (size_t)len[k];
-      sk::FoldAliSeq f;
-      f.row_off = (int64_t)codes.size();
-      f.work_off = (int64_t)work;
-      f.out_off = (int64_t)outn;
-      f.n = (int32_t)nn;
-      f.n_rows = n_rows[k];
-      for (size_t r = first[k]; r < first[k + 1]; ++r)
-        for (size_t a = 0; a < nn; ++a) codes.push_back(fold_code(rows[r][a]));
-      if (no_lp) {
-        f.lp_off = (int64_t)lp.size();
-        lp.resize(lp.size() + nn * nn);
-        lonely_pair_table_ali(codes.data() + f.row_off, n_rows[k], (int)nn, L.F.no_gu != 0, lp.data() + f.lp_off);
-      }
-      work += sk::fold_ali_work_doubles(nn);
-      outn += nn > 1 ? nn * (nn - 1) / 2 : 0;
-      bmax = std::max(bmax, (int)nn);
-      sq.push_back(f);
-    }
-    const int nb = b1 - b0;
-    // the fold's tables, then the energies the per-cell phase sums over the rows
-    fold_tables(bmax, L.F, tab);
-    L.o_ali = (int32_t)tab.size();
-    for (int a = 0; a < 8; ++a)
-      for (int b = 0; b < 8; ++b)
-        tab.push_back(a >= 1 && a <= 6 && b >= 1 && b <= 6 ? (double)sk::foldp::stack37[a][b] : 0.0);
-    tab.push_back(sk::foldp::kT);
-    tab.push_back((double)sk::foldp::terminal_au);
-    tab.push_back((double)sk::foldp::bulge37[1]);
-    L.F.n_tab = (int32_t)tab.size();
-    L.F.n_tab_pad = (L.F.n_tab + 1) & ~1;
-    if (sk::fold_ali_lds_bytes(L.F, bmax) > sk::kFoldLdsMax)
-      return fail(ctx, SK_ERR_UNSUPPORTED, "consensus fold: alignment too long for the kernel's LDS");
-    const size_t need = sq.size() * sizeof(sk::FoldAliSeq) + codes.size() + lp.size() + tab.size() * 8 +
-                        (outn + nb) * 8 + 10 * 256;
-    int rc = ensure_work(ctx, need);
-    if (rc) return rc;
-    rc = ensure_scratch(ctx, std::max<size_t>(work * 8, 64));
-    if (rc) return rc;
-    Arena A{static_cast<char*>(ctx->work), 0, ctx->work_bytes};
-    sk::FoldAliSeq* d_sq = A.take<sk::FoldAliSeq>(sq.size());
-    int8_t* d_codes = A.take<int8_t>(std::max<size_t>(codes.size(), 1));
-    double* d_tab = A.take<double>(tab.size());
-    double* d_out = A.take<double>(std::max<size_t>(outn, 1));
-    double* d_lz = A.take<double>(nb);
-    uint8_t* d_lp = no_lp ? A.take<uint8_t>(std::max<size_t>(lp.size(), 1)) : nullptr;
-    if (no_lp && !lp.empty()) SK_HIP(ctx, hipMemcpyAsync(d_lp, lp.data(), lp.size(), hipMemcpyHostToDevice, S));
-    SK_HIP(ctx, hipMemcpyAsync(d_sq, sq.data(), sq.size() * sizeof(sk::FoldAliSeq), hipMemcpyHostToDevice, S));
-    if (!codes.empty())
-      SK_HIP(ctx, hipMemcpyAsync(d_codes, codes.data(), codes.size(), hipMemcpyHostToDevice, S));
-    SK_HIP(ctx, hipMemcpyAsync(d_tab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, S));
-    SK_HIP(ctx, hipMemsetAsync(ctx->scratch, 0, work * 8, S));
-    SK_HIP(ctx, hipMemsetAsync(d_out, 0, std::max<size_t>(outn, 1) * 8, S));
-    L.F.lp = d_lp;
-    L.F.tab = d_tab;
-    L.F.work = ctx->scratch;
-    L.F.out = d_out;
-    L.F.log_z = d_lz;
-    L.alns = d_sq;
-    L.codes = d_codes;
-    SK_HIP(ctx, sk::launch_fold_ali(L, nb, bmax, S));
-    std::vector<double> lz(nb);
-    if (outn) SK_HIP(ctx, hipMemcpyAsync(out + out_host, d_out, outn * 8, hipMemcpyDeviceToHost, S));
-    SK_HIP(ctx, hipMemcpyAsync(lz.data(), d_lz, nb * 8, hipMemcpyDeviceToHost, S));
-    SK_HIP(ctx, hipStreamSynchronize(S));
-    for (int k = 0; k < nb; ++k) {
-      if (!std::isfinite(lz[k]))
-        return fail(ctx, SK_ERR_UNSUPPORTED,
-                    "consensus fold: partition function out of double range (alignment too long)");
-      if (log_z) log_z[b0 + k] = lz[k];
-    }
-    out_host += outn;
-    b0 = b1;
-  }
-  return SK_OK;
+  return fold_batches(ctx, kFoldAli, n_aln, n_rows, rows, flags, out, log_z, nullptr);
 }
 
 namespace {
