@@ -188,19 +188,29 @@ __global__ void __launch_bounds__(512) sk_fold_kernel(FoldLaunch P) {
 #endif
 }
 
-static size_t fold_lds_bytes_t(const FoldLaunch& P, int max_n, bool gtab) {
-  const bool ring = fold_ring(max_n);
+// the dynamic LDS of sk_fold_kernel<ring, gtab>
+static size_t fold_lds_bytes_t(const FoldLaunch& P, int max_n, bool ring, bool gtab) {
   const size_t ntab = gtab ? (size_t)((P.n_small + 1) & ~1) : (size_t)P.n_tab_pad;
   return (ntab + (ring ? (size_t)kFoldRing * max_n : 0)) * 8 + (size_t)(max_n + 15) / 16 * 16;
 }
 
-bool fold_gtab(const FoldLaunch& P, int max_n) { return fold_lds_bytes_t(P, max_n, false) > kFoldLdsMax; }
+bool fold_ring(const FoldLaunch& P, int max_n) { return max_n <= kFoldRingMaxN && P.min_path == kFoldPathRing; }
 
-size_t fold_lds_bytes(const FoldLaunch& P, int max_n) {
-  return fold_lds_bytes_t(P, max_n, fold_gtab(P, max_n));
+// (a launch with the ring has at most kFoldRingMaxN nucleotides: its tables always fit)
+bool fold_gtab(const FoldLaunch& P, int max_n) {
+  if (fold_ring(P, max_n)) return false;
+  return P.min_path == kFoldPathGtab || fold_lds_bytes_t(P, max_n, false, false) > kFoldLdsMax;
 }
 
-bool fold_ring(int max_n) { return max_n <= kFoldRingMaxN; }
+FoldPath fold_path(const FoldLaunch& P, int max_n) {
+  return fold_ring(P, max_n) ? kFoldPathRing : fold_gtab(P, max_n) ? kFoldPathGtab : kFoldPathHbm;
+}
+
+// one decision (fold_path) gives a launch's LDS size and its kernel
+size_t fold_lds_bytes(const FoldLaunch& P, int max_n) {
+  const FoldPath path = fold_path(P, max_n);
+  return fold_lds_bytes_t(P, max_n, path == kFoldPathRing, path == kFoldPathGtab);
+}
 
 hipError_t launch_fold(const FoldLaunch& P0, int n_seqs, int max_n, hipStream_t st) {
   if (n_seqs <= 0) return hipSuccess;
@@ -208,9 +218,10 @@ hipError_t launch_fold(const FoldLaunch& P0, int n_seqs, int max_n, hipStream_t 
   P.max_n = max_n;
   const size_t lds = fold_lds_bytes(P, max_n);
   if (lds > kFoldLdsMax) return hipErrorInvalidValue;
-  const bool ring = fold_ring(max_n);  // (its tables always fit)
-  return launch_fold_kernel(ring ? sk_fold_kernel<true, false>
-                                 : fold_gtab(P, max_n) ? sk_fold_kernel<false, true> : sk_fold_kernel<false, false>,
+  const FoldPath path = fold_path(P, max_n);
+  return launch_fold_kernel(path == kFoldPathRing   ? sk_fold_kernel<true, false>
+                            : path == kFoldPathGtab ? sk_fold_kernel<false, true>
+                                                    : sk_fold_kernel<false, false>,
                             P, dim3(n_seqs), 512, lds, st);
 }
 

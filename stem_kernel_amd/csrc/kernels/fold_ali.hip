@@ -217,8 +217,13 @@ __global__ void __launch_bounds__(512) sk_fold_ali_kernel(FoldLaunch P) {
   }
 }
 
+FoldPath fold_ali_path(const FoldLaunch& P, int max_n) {
+  return max_n <= kFoldRingMaxN && P.min_path != kFoldPathHbm ? kFoldPathRing : kFoldPathHbm;
+}
+
 size_t fold_ali_lds_bytes(const FoldLaunch& P, int max_n) {
-  return ((size_t)P.n_tab_pad + (fold_ring(max_n) ? (size_t)kFoldRing * max_n : 0)) * 8;
+  const bool ring = fold_ali_path(P, max_n) == kFoldPathRing;
+  return ((size_t)P.n_tab_pad + (ring ? (size_t)kFoldRing * max_n : 0)) * 8;
 }
 
 hipError_t launch_fold_ali(const FoldLaunch& P0, int n_alns, int max_n, hipStream_t st) {
@@ -227,8 +232,9 @@ hipError_t launch_fold_ali(const FoldLaunch& P0, int n_alns, int max_n, hipStrea
   P.max_n = max_n;
   const size_t lds = fold_ali_lds_bytes(P, max_n);
   if (lds > kFoldLdsMax) return hipErrorInvalidValue;
-  return launch_fold_kernel(fold_ring(max_n) ? sk_fold_ali_kernel<true> : sk_fold_ali_kernel<false>, P,
-                            dim3(n_alns), 512, lds, st);
+  const bool ring = fold_ali_path(P, max_n) == kFoldPathRing;
+  return launch_fold_kernel(ring ? sk_fold_ali_kernel<true> : sk_fold_ali_kernel<false>, P, dim3(n_alns), 512, lds,
+                            st);
 }
 
 }  // namespace sk

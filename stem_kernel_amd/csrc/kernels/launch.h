@@ -303,6 +303,8 @@ struct FoldLaunch {
   double* log_z = nullptr;        // per item of the launch (nullptr: not wanted)
   int32_t inside_only = 0;        // fold.hip: stop after the inside pass and Q5 (the sampler's input)
   int32_t o_ali = 0;              // fold_ali.hip, in tab: the row energies (host: fold_tables_ali)
+  int32_t min_path = 0;           // host only, a FoldPath: the launch takes no path before it (experiments
+                                  // build, SK_FOLD_PATH; 0: the launch's own choice)
 };
 
 // Work buffer of one item: `tables` n x n tables by diagonal (cell (i, i+d)
@@ -335,10 +337,19 @@ inline size_t fold_ali_work_doubles(size_t n) { return FoldWork::doubles(kFoldAl
 constexpr int kFoldRingMaxN = 248;
 // dynamic LDS a fold launch may take (160 KB less the kernel's static block sums)
 constexpr size_t kFoldLdsMax = 163840 - 256;
-bool fold_ring(int max_n);
-// whether a launch keeps the hairpin / scale tables in HBM (they and the ring
-// and codes would not fit the LDS)
+// The kernel a fold launch runs, in the order a launch may be pushed along
+// (FoldLaunch::min_path): the LDS ring; no ring, the tables in LDS; no ring and
+// only the fixed head of the tables in LDS.  The LDS size, the kernel and the
+// name the batch driver reports all come from fold_ring / fold_gtab.
+enum FoldPath : int32_t { kFoldPathRing = 0, kFoldPathHbm = 1, kFoldPathGtab = 2 };
+bool fold_ring(const FoldLaunch& P, int max_n);
+// whether a launch keeps the hairpin / scale tables in HBM (they and the codes
+// would not fit the LDS; a launch with the ring never does)
 bool fold_gtab(const FoldLaunch& P, int max_n);
+inline const char* fold_path_name(FoldPath p) {
+  return p == kFoldPathRing ? "ring" : p == kFoldPathHbm ? "hbm" : "gtab";
+}
+FoldPath fold_path(const FoldLaunch& P, int max_n);
 size_t fold_lds_bytes(const FoldLaunch& P, int max_n);
 hipError_t launch_fold(const FoldLaunch& P, int n_seqs, int max_n, hipStream_t st);
 
@@ -362,6 +373,9 @@ hipError_t launch_fold_sample(const FoldSampleLaunch& P, int n_seqs, int max_n, 
 
 // Consensus fold of alignments (fold_ali.hip): the fold's passes over
 // per-cell tables a first phase fills from the rows (FoldLaunch::o_ali)
+// (ring or hbm: the kernel has no variant that reads tables from HBM, so of
+// FoldLaunch::min_path it honours kFoldPathHbm alone)
+FoldPath fold_ali_path(const FoldLaunch& P, int max_n);
 size_t fold_ali_lds_bytes(const FoldLaunch& P, int max_n);
 hipError_t launch_fold_ali(const FoldLaunch& P, int n_alns, int max_n, hipStream_t st);
 

@@ -4072,6 +4072,7 @@ struct FoldKind {
   double (*more_bytes)(double n, double rows, bool no_lp);  // an item's share of the memory budget besides them
   void (*lonely)(const int8_t* c, int n_rows, int n, bool no_gu, uint8_t* lp);  // --noLonelyPairs filter of an item
   void (*more_tables)(sk::FoldLaunch&, std::vector<double>&);                   // after fold_tables (nullptr: none)
+  sk::FoldPath (*path)(const sk::FoldLaunch&, int);  // the kernel a launch runs (lds_bytes and launch go by it)
   size_t (*lds_bytes)(const sk::FoldLaunch&, int);
   hipError_t (*launch)(const sk::FoldLaunch&, int, int, hipStream_t);
   const char *too_long, *out_of_range;  // the wording of its errors
@@ -4079,11 +4080,12 @@ struct FoldKind {
 const FoldKind kFoldPlain = {
     sk::kFoldTables, [](double, double, bool) { return 0.0; },
     [](const int8_t* c, int, int n, bool no_gu, uint8_t* lp) { sk::lonely_pair_table(c, n, no_gu, lp); }, nullptr,
-    sk::fold_lds_bytes, sk::launch_fold, "fold: sequence too long for the fold kernel's LDS",
+    sk::fold_path, sk::fold_lds_bytes, sk::launch_fold, "fold: sequence too long for the fold kernel's LDS",
     "fold: partition function out of double range (sequence too long)"};
 const FoldKind kFoldAli = {
     sk::kFoldAliTables, [](double n, double rows, bool no_lp) { return n * rows + (no_lp ? n * n : 0.0); },
-    sk::lonely_pair_table_ali, sk::fold_tables_ali, sk::fold_ali_lds_bytes, sk::launch_fold_ali,
+    sk::lonely_pair_table_ali, sk::fold_tables_ali, sk::fold_ali_path, sk::fold_ali_lds_bytes,
+    sk::launch_fold_ali,
     "consensus fold: alignment too long for the kernel's LDS",
     "consensus fold: partition function out of double range (alignment too long)"};
 
@@ -4120,6 +4122,15 @@ int fold_batches(sk_context* ctx, const FoldKind& K, int32_t n, const int32_t* n
   SK_HIP(ctx, hipMemGetInfo(&free_b, &total_b));
   double budget = std::min(16e9, 0.4 * (double)free_b);
   if (const char* e = SK_KNOB("SK_FOLD_BUDGET")) budget = std::atof(e);
+  // experiments build: SK_FOLD_PATH = hbm | gtab keeps the launches off the LDS
+  // ring / also leaves the hairpin and scale tables in HBM, so a test can run
+  // those kernels on short items (read per call)
+  if (const char* e = SK_KNOB("SK_FOLD_PATH")) {
+    if (!std::strcmp(e, "hbm")) L.min_path = sk::kFoldPathHbm;
+    else if (!std::strcmp(e, "gtab")) L.min_path = sk::kFoldPathGtab;
+    else return fail(ctx, SK_ERR_INVALID, "SK_FOLD_PATH: hbm or gtab");
+  }
+  const bool stats = std::getenv("SK_HOST_STATS") != nullptr;
   hipStream_t S = ctx->stream;
   size_t out_host = 0;  // packed outputs of the batches before (host)
   size_t str_host = 0;  // sampled structures written so far (host)
@@ -4197,6 +4208,9 @@ int fold_batches(sk_context* ctx, const FoldKind& K, int32_t n, const int32_t* n
     L.work = ctx->scratch;
     L.out = d_out;
     L.log_z = d_lz;
+    if (stats)
+      std::fprintf(stderr, "[sk] fold batch: %d items, longest %d, path %s\n", nb, bmax,
+                   sk::fold_path_name(K.path(L, bmax)));
     SK_HIP(ctx, K.launch(L, nb, bmax, S));
     std::vector<double> lz(nb);
     std::vector<uint32_t> cnt;
@@ -4237,7 +4251,7 @@ int fold_batches(sk_context* ctx, const FoldKind& K, int32_t n, const int32_t* n
     str_host += strn;
     b0 = b1;
   }
-  if (std::getenv("SK_HOST_STATS")) std::fprintf(stderr, "[sk] fold: %d items in %d batches\n", (int)n, n_batches);
+  if (stats) std::fprintf(stderr, "[sk] fold: %d items in %d batches\n", (int)n, n_batches);
   return SK_OK;
 }
 

@@ -23,6 +23,7 @@ import pytest
 import stem_kernel_amd as ska
 from oracle import pyoracle as po
 from tests import alifold_ref as ar
+from tests.helpers import fold_paths
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CLI = os.path.join(ROOT, "stem_kernel_amd", "bin", "stem_kernel_lite")
@@ -257,16 +258,27 @@ def test_compat_header_consensus_option(tmp_path):
 # ------------------------------------------------------------------ GPU
 @pytest.mark.gpu
 @pytest.mark.parametrize("flags", [{}, {"no_gu": True}, {"no_lonely_pairs": True}])
-def test_gpu_identical_rows_equal_the_fold(gpu_ctx, flags):
+def test_gpu_identical_rows_equal_the_fold(gpu_ctx, monkeypatch, capfd, flags):
     """One row, and three identical rows, are the single-sequence fold: the
-    LDS-ring path (n <= 248) and the path without it (249)."""
+    LDS-ring path (n <= 248) and the path without it (249).  The path is the
+    launch's, chosen by its longest item, so the 249-mer goes in calls of its
+    own; which kernel ran is read from the driver's batch lines."""
     rng = np.random.default_rng(31)
     seqs = [_rand_seq(rng, n) for n in (5, 36, 248, 249)]
-    ref, ref_z = gpu_ctx.fold(seqs, log_z=True, **flags)
-    got, lz = gpu_ctx.fold_alignment([[s] for s in seqs] + [[s] * 3 for s in seqs], with_log_z=True, **flags)
+    ref, ref_z, got, lz = [], [], [], []
+    for part, path in ((seqs[:3], "ring"), (seqs[3:], "hbm")):
+        (r, rz), b_fold = fold_paths(capfd, monkeypatch, lambda: gpu_ctx.fold(part, log_z=True, **flags))
+        (g, gz), b_ali = fold_paths(capfd, monkeypatch, lambda: gpu_ctx.fold_alignment(
+            [[s] for s in part] + [[s] * 3 for s in part], with_log_z=True, **flags))
+        assert b_fold == [(len(part), len(part[-1]), path)] and b_ali == [(2 * len(part), len(part[-1]), path)]
+        ref += list(r) + list(r)
+        ref_z += list(rz) + list(rz)
+        got += list(g)
+        lz += list(gz)
+    assert len(got) == 2 * len(seqs)
     assert any(np.max(p, initial=0.0) > 0.1 for p in ref)
-    for k in range(2 * len(seqs)):
-        _close(lz[k], got[k], ref_z[k % len(seqs)], ref[k % len(seqs)])
+    for k in range(len(got)):
+        _close(lz[k], got[k], ref_z[k], ref[k])
 
 
 @pytest.mark.gpu
@@ -295,6 +307,21 @@ def test_gpu_mutated_alignments_equal_dp(gpu_ctx, n, S):
         ref_z, ref_p = _dp(tuple(rows), *flags)
         assert np.max(ref_p) > 0.1
         _close(lz[0], got[0], ref_z, ref_p)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("flags", [(False, False), (True, False), (False, True)])
+def test_gpu_longest_ring_alignment_equals_dp(gpu_ctx, monkeypatch, capfd, flags):
+    """248 columns x 3 rows alone: the longest alignment the LDS-ring kernel
+    takes (the 249-column, no-ring case is in test_gpu_mixed_call_keeps_order)."""
+    rows = _mutated_alignment(np.random.default_rng(248003), 248, 3)
+    assert any("-" in r for r in rows) and len(set(rows)) == 3
+    (got, lz), batches = fold_paths(capfd, monkeypatch, lambda: gpu_ctx.fold_alignment(
+        [rows], no_gu=flags[0], no_lonely_pairs=flags[1], with_log_z=True))
+    assert batches == [(1, 248, "ring")]
+    ref_z, ref_p = _dp(tuple(rows), *flags)
+    assert np.max(ref_p) > 0.1
+    _close(lz[0], got[0], ref_z, ref_p)
 
 
 @pytest.mark.gpu

@@ -37,7 +37,8 @@ def test_shipped_library_reads_no_switches():
 
 def test_experiments_build_has_the_switches():
     names = _sk_strings(EXP)
-    for k in ("SK4_NO_GSUM", "SK4_SPAN", "SK_NO_GAMMA", "SK_STR_GENERAL", "SK_BPLA_GENERAL", "SK_FORCE_BIG_Y"):
+    for k in ("SK4_NO_GSUM", "SK4_SPAN", "SK_NO_GAMMA", "SK_STR_GENERAL", "SK_BPLA_GENERAL", "SK_FORCE_BIG_Y",
+              "SK_FOLD_PATH"):
         assert k in names, k
 
 

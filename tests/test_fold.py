@@ -9,7 +9,9 @@ model is the Turner-1999 core).  Pinned here instead:
   random short sequences, with and without --noGU / --noClosingGU /
   --noLonelyPairs (the legacy ViennaRNA pair-type filter, restated);
 * the GPU fold equals the oracle's DP (1e-9 absolute on probabilities, 1e-12
-  relative on ln Z) up to L = 400, single sequences and batches;
+  relative on ln Z) up to L = 400, single sequences and batches -- every call
+  here with a sequence of more than 248 nt runs without the LDS ring; the ring
+  kernel, the boundary and 530 nt are in test_fold_paths.py;
 * probabilities are a distribution per base (sum_j p(i,j) <= 1), and the
   threaded dataset builders give the same DAG as the one-at-a-time path.
 """
@@ -142,9 +144,17 @@ def test_gpu_fold_no_lonely_pairs(gpu_ctx, no_gu):
 def test_gpu_fold_tables_sized_per_batch(gpu_ctx):
     """the Boltzmann tables are sized by each launch's longest
     sequence (sk_fold_mccaskill builds them per batch), so short sequences
-    fold the same -- on the LDS-ring path -- alone and in a call with a
-    1,200-nt sequence (no ring; its hairpin / scale tables 19 KB longer); the
-    long one against the oracle's ln Z."""
+    fold the same alone -- on the LDS-ring path -- and in a call with a
+    1,200-nt sequence, whose launch runs without the ring for all four and
+    with hairpin / scale tables 19 KB longer; the long one against the
+    oracle's ln Z (the inside pass).
+
+    What this does not cover: those tables are about 21 KB and still sit in
+    LDS.  The kernel that reads them from HBM (sk_fold_kernel<false, true>) is
+    selected when 8 n_tab_pad + the padded codes pass 163,584 bytes, n_tab =
+    151 + (L + 2) + (L + 3): from about 9,550 nt, where Z has long left the
+    double range (~1,400 nt).  test_fold_paths.py runs it through the
+    experiments build's SK_FOLD_PATH, and checks probabilities past 512 nt."""
     rng = np.random.default_rng(77)
     short = [_rand_seq(rng, L) for L in (12, 60, 150)]
     long_ = _rand_seq(rng, 1200)

@@ -28,6 +28,7 @@ import pytest
 import stem_kernel_amd as ska
 from oracle import pyoracle as po
 from stem_kernel_amd._lib import SIGNATURES, lib
+from tests.helpers import fold_paths
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIBDIR = os.path.join(ROOT, "stem_kernel_amd")
@@ -214,11 +215,15 @@ def test_gpu_structure_distribution(gpu_ctx, name, f):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("length,s", [(40, 8192), (75, 8192), (200, 4096)])
+@pytest.mark.parametrize("length,s", [(40, 8192), (75, 8192), (200, 4096), (260, 4096)])
 @pytest.mark.parametrize("f", FLAGS)
-def test_gpu_pair_marginals(gpu_ctx, length, s, f):
+def test_gpu_pair_marginals(gpu_ctx, monkeypatch, capfd, length, s, f):
+    """260 nucleotides: the inside launch whose tables the sampler walks runs
+    without the LDS ring (more than 248), the others with it."""
     seq = _random(length)
-    bpp, lz = gpu_ctx.fold_sample([seq], s, seed=3, log_z=True, **_kw(f))
+    (bpp, lz), batches = fold_paths(capfd, monkeypatch,
+                                    lambda: gpu_ctx.fold_sample([seq], s, seed=3, log_z=True, **_kw(f)))
+    assert batches == [(1, length, "ring" if length <= 248 else "hbm")]
     ref_z, ref = _oracle(seq, f)
     dev = np.abs(bpp[0] - ref)
     lim = _bound(ref, s)
@@ -242,7 +247,10 @@ def test_gpu_keying(gpu_ctx):
     # the sequence index is a key: a sequence moved to another place in the call draws other samples
     _, se = gpu_ctx.fold_sample(seqs[::-1], 100, seed=4, structures=True)
     assert se[1] != sd[0]
-    # a 1,200-nt sequence in the call (no LDS ring, hairpin / scale tables in HBM, longer tables)
+    # a 1,200-nt sequence in the call: no LDS ring for any sequence of the launch and tables 19 KB longer,
+    # still in LDS (about 21 KB), its ln Z against the oracle.  The kernel that reads the hairpin / scale
+    # tables from HBM takes over from about 9,550 nt only (8 (2 L + 156) + L > 163,584 bytes), past the
+    # double range: test_fold_paths.py runs it (SK_FOLD_PATH=gtab) and the sampler after it.
     long_ = _random(1200)
     short = gpu_ctx.fold_sample(seqs, 100, seed=4)
     both, lz = gpu_ctx.fold_sample(seqs + [long_], 100, seed=4, log_z=True)
