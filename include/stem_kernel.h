@@ -473,7 +473,9 @@ int sk_last_timing(const sk_context *ctx, double *stem_ms, double *string_ms,
  * stem, 4-D stem or BPLA), each timed by HIP events around it on its own
  * stream, and their count: *ms_sum / *n_launches is the average launch
  * duration a kernel-trace profiler reports.  Launches on several streams
- * overlap, so the sum can exceed sk_last_timing's span. */
+ * overlap, so the sum can exceed sk_last_timing's span.  The DAG stem
+ * launches' shared Gamma tables are built by kernels of their own ahead of
+ * all launches (0.5 ms of a 4.7 s step); these are in the span, not here. */
 int sk_last_launch_ms(const sk_context *ctx, double *ms_sum, int32_t *n_launches);
 /* Asynchronous compute calls (default off).  With on != 0, sk_pairs_device
  * (and every call that returns its results on the device) returns once its
@@ -496,6 +498,13 @@ int sk_sync_timing(sk_context *ctx);
  * lane), shifted by 4 for the banded (partial_dp) variant and by 8 for the
  * column-pipelined full_dp kernel. */
 int sk_last_classes(const sk_context *ctx, uint32_t *stem_maxk_mask, uint32_t *stem4d_mask);
+/* The number of DAG stem class launches of the last compute call that read one
+ * Gamma table per y example, built by a table kernel ahead of the launch and
+ * shared by every workgroup on that y (0 for a null context).  The other
+ * launches -- x sets without gamma keys, classes without a gapless y, tables
+ * beyond the memory budget -- build a table per workgroup and work item
+ * (diagnostic: which path ran). */
+int32_t sk_last_gamma_shared(const sk_context *ctx);
 /* Shape the column-pipelined 4-D kernel takes for a full_dp Gram batch whose
  * x and y examples have lengths [min_len, max_len]: *nb chained columns per
  * group, *waves waves per pair, *pf rows fetched ahead per wave (diagnostic;

@@ -18,7 +18,10 @@
 // Parallel structure: one WAVEFRONT per (x,y) pair; a workgroup of W waves
 // shares one y example (its DAG staged once in LDS) and pulls x examples from
 // a per-item LDS cursor; workgroups pull items from a global counter
-// (persistent grid).  No MFMA: this is a recurrence, not a contraction.
+// (persistent grid).  The Gamma tables of a launch's y's are built once, by
+// sk_gamma_table_kernel ahead of the stem launches, and shared by the
+// workgroups on a y.
+// No MFMA: this is a recurrence, not a contraction.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -974,55 +977,61 @@ struct StemWaves {
   static constexpr int value = MAXK <= 12 ? 12 : MAXK <= 17 ? (SK_M16 ? 12 : SK_W16) : MAXK <= 20 ? SK_W20 : 8;
 };
 
+// The LDS regions of a stem workgroup (every region a multiple of 16 bytes;
+// stem_lds_bytes); the Gamma table kernel uses the same carve
+struct StemLds {
+  lds_f64* co;     // 256
+  lds_f64* gp;     // n_gpow_pad
+  lds_f64* Rall;   // nwaves*maxnl
+  lds_f64* hball;  // nwaves*64*PW (MATCH sums)
+  lds_f64* yew;    // lds_max_nch*64 weights (node weights: maxnl)
+  lds_u32* ysc;    // lds_max_nch*64 records
+  lds_u32* yed2;   // lds_max_edges (mult. of 4)
+  lds_i32* ylf;    // lds_max_len_pad
+  lds_i32* ycs;    // lds_max_len_pad
+  lds_i32* ctl;    // 4 ints
+  lds_f64* kap;    // xset.n_gam (gam_on)
+};
+
 template <int MAXK>
-__global__ void __launch_bounds__(64 * StemWaves<MAXK>::value) sk_dag_stem_kernel(StemLaunch P) {
+__device__ __forceinline__ StemLds stem_lds_carve(const StemLaunch& P, int nwaves) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const DevSet& s = P.yset;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int nwaves = blockDim.x >> 6;
-  const int maxnl = P.lds_max_nl;  // multiple of 64
+  const int maxnl = P.lds_max_nl;
   constexpr int PW = pass_width<MAXK>();
-
-  // LDS carve (every region a multiple of 16 bytes)
-  lds_f64* co = (lds_f64*)(smem);                             // 256
-  lds_f64* gp = co + 256;                                     // n_gpow_pad
-  lds_f64* Rall = gp + P.n_gpow_pad;                          // nwaves*maxnl
-  lds_f64* hball = Rall + (size_t)nwaves * maxnl;             // nwaves*64*PW (MATCH sums)
   constexpr bool NW = node_weights<MAXK>();
-  lds_f64* yew = hball + (size_t)nwaves * 64 * PW;         // lds_max_nch*64 weights (NW: maxnl)
-  lds_u32* ysc = (lds_u32*)(yew + (node_weights_f32<MAXK>() ? (size_t)maxnl / 2
-                                   : NW ? (size_t)maxnl : (size_t)P.lds_max_nch * 64));  // lds_max_nch*64 records
-  lds_u32* yed2 = ysc + (size_t)P.lds_max_nch * 64;           // lds_max_edges (mult. of 4)
-  lds_i32* ylf = (lds_i32*)(yed2 + (edges_global<MAXK>() ? 0 : P.lds_max_edges));  // lds_max_len_pad
-  lds_i32* ycs = ylf + P.lds_max_len_pad;                     // lds_max_len_pad
-  lds_i32* ctl = ycs + P.lds_max_len_pad;                     // 4 ints
-  lds_f64* kap = (lds_f64*)(ctl + 4);                         // xset.n_gam (gam_on)
+  StemLds L;
+  L.co = (lds_f64*)(smem);
+  L.gp = L.co + 256;
+  L.Rall = L.gp + P.n_gpow_pad;
+  L.hball = L.Rall + (size_t)nwaves * maxnl;
+  L.yew = L.hball + (size_t)nwaves * 64 * PW;
+  L.ysc = (lds_u32*)(L.yew + (node_weights_f32<MAXK>() ? (size_t)maxnl / 2
+                              : NW ? (size_t)maxnl : (size_t)P.lds_max_nch * 64));
+  L.yed2 = L.ysc + (size_t)P.lds_max_nch * 64;
+  L.ylf = (lds_i32*)(L.yed2 + (edges_global<MAXK>() ? 0 : P.lds_max_edges));
+  L.ycs = L.ylf + P.lds_max_len_pad;
+  L.ctl = L.ycs + P.lds_max_len_pad;
+  L.kap = (lds_f64*)(L.ctl + 4);
+  return L;
+}
 
-  for (int k = threadIdx.x; k < 256; k += blockDim.x) co[k] = P.co_subst[k];
-  for (int k = threadIdx.x; k < P.n_gpow; k += blockDim.x) gp[k] = P.gpow[k];
-
-  lds_f64* R = Rall + (size_t)wave * maxnl;
-  lds_f64* hb = hball + (size_t)wave * 64 * PW;
-  for (int j = 0; j < PW; ++j) hb[64 * j + lane] = 0.0;  // kept zero between MATCH passes
-  double* slab = P.scratch + (size_t)(blockIdx.x * nwaves + wave) * P.slab_doubles;
-  double* gamtab = P.gam_on ? P.gam + (size_t)blockIdx.x * P.gam_doubles : nullptr;
-  // the workgroup's Phi table: n_phi rows of 64*MAXK, then their sums kappa
-  double* phitab = P.phi_on ? P.phi + (size_t)blockIdx.x * P.phi_doubles : nullptr;
-  double* phikap = P.phi_on ? phitab + (size_t)P.xset.n_phi * (64 * MAXK) : nullptr;
+// Stages the y example in the workgroup's LDS (sweep schedule and weights,
+// node-major edges, length tables) and fills its view.  Every thread of the
+// workgroup calls it, behind a barrier that follows the gp fill (read here
+// ahead of the first barrier); the data are visible to all on return.
+template <int MAXK>
+__device__ __forceinline__ void stage_y(const StemLaunch& P, const StemLds& L, int y, YView& Y) {
+  const DevSet& s = P.yset;
+  constexpr bool NW = node_weights<MAXK>();
+  const int maxnl = P.lds_max_nl;  // multiple of 64
   const double gap2 = P.gap2;
-  const int band = (int)P.band;
-
-  // wave index as an SGPR value: every branch below on it is wave-uniform
-  const int wave_u = __builtin_amdgcn_readfirstlane(wave);
-  for (;;) {
-    __syncthreads();
-    if (threadIdx.x == 0) ctl[0] = atomicAdd(P.item_counter, 1);
-    __syncthreads();
-    const int it = __builtin_amdgcn_readfirstlane(ctl[0]);
-    if (it >= P.n_items) break;
-    const int4 item = P.items[it];  // {y, base, count, -}
-    const int y = item.x;
-    YView Y;
+  lds_f64* gp = L.gp;
+  lds_f64* yew = L.yew;
+  lds_u32* ysc = L.ysc;
+  lds_u32* yed2 = L.yed2;
+  lds_i32* ylf = L.ylf;
+  lds_i32* ycs = L.ycs;
+  {
     Y.nl = s.ex_nl[y];
     Y.nch = s.ex_nch[y];
     Y.nseqs = s.ex_nseqs[y];
@@ -1074,52 +1083,145 @@ __global__ void __launch_bounds__(64 * StemWaves<MAXK>::value) sk_dag_stem_kerne
       ylf[v] = lo;
     }
     __syncthreads();
+  }
+}
 
-    // Gamma rows of this y (gapless y only): for every gamma key g = (code,
-    // len) of the x set, Gamma_g = the IY sweep of M_g[q] = co[code][bp(q)]
-    // p(q) g^{leaf gaps(q)} over the y loop nodes q in len's length band (an
-    // x gamma row's G0 row is g^lg pf Gamma_g; its MATCH row is that times
-    // M_g), into this workgroup's table; kappa_g = sum_q M_g[q] P_y[q].
+// Gamma rows of the staged y (gapless y only): for every gamma key g = (code,
+// len) of the x set, Gamma_g = the IY sweep of M_g[q] = co[code][bp(q)]
+// p(q) g^{leaf gaps(q)} over the y loop nodes q in len's length band (an
+// x gamma row's G0 row is g^lg pf Gamma_g; its MATCH row is that times
+// M_g), into the table gamtab; kappa_g = sum_q M_g[q] P_y[q], into kap (LDS
+// in the stem kernel, HBM in the table kernel).  Wave w of the workgroup
+// takes the keys w, w + nwaves, ...; R is its LDS row.  The stem kernel's
+// per-workgroup tables and the table kernel's shared ones come from this one
+// code: the same operations on the same operands in the same order.
+template <int MAXK, typename KapPtr>
+__device__ __forceinline__ void gamma_rows(const StemLaunch& P, const YView& Y, lds_f64* R, const lds_f64* co,
+                                           const lds_f64* gp, double* gamtab, KapPtr kap, int wave_u,
+                                           int nwaves, int lane) {
+  const DevSet& s = P.yset;
+  const DevSet& xset = P.xset;
+  const int band = (int)P.band;
+  const int nb = Y.nb, bb = Y.bb;
+  for (int g = wave_u; g < xset.n_gam; g += nwaves) {
+    const uint32_t key = xset.gam_key[g];
+    const int gcode = (int)(key >> 16) * 16, glen = (int)(key & 0xffff);
+    double kp = 0.0;
+    for (int k = 0; k < MAXK; ++k) {
+      const int q = lane + 64 * k;
+      double M = 0.0;
+      if (q < Y.nl) {
+        const uint4 nd = Y.nrg[q];
+        const int ylen = (int)(s.yn_b[nb + q] & 0xffff);
+        if (((nd.x >> 16) & 0xff) == 0 && (band == 0 || abs(glen - ylen) <= band)) {
+          double vs;
+          if ((nd.y >> 24) != 0u) {
+            vs = co[gcode + ((nd.y >> 16) & 0xf)] * (double)__uint_as_float(nd.w);
+          } else {
+            vs = 0.0;
+            const int yb0 = (int)(s.yn_b[nb + q] >> 16), ynb = (int)(nd.x >> 24);
+            for (int b = 0; b < ynb; ++b)
+              vs += co[gcode + s.bpf_code[bb + yb0 + b]] * (double)s.bpf_p[bb + yb0 + b];
+          }
+          M = vs * gp[nd.y & 0xffff];
+          kp += M * s.yn_P[nb + q];
+        }
+      }
+      R[q] = M;
+    }
+    for (int off = 32; off > 0; off >>= 1) kp += __shfl_xor(kp, off, 64);
+    if (lane == 0) kap[g] = kp;
+    wave_sync();
+    int c0 = 0;
+    if (band > 0) c0 = Y.ycs[min(max(glen - band, 0), Y.lmax + 1)];
+    c0 = __builtin_amdgcn_readfirstlane(c0);
+    if (c0 < Y.nch) iy_sweep<node_weights<MAXK>(), node_weights_f32<MAXK>()>(Y, R, c0, lane);
+    double* grow = gamtab + (size_t)g * (64 * MAXK);
+    for (int k = 0; k < MAXK; ++k)
+      if (lane + 64 * k < Y.nl) grow[lane + 64 * k] = R[lane + 64 * k];  // (the tail is never read)
+    wave_sync();
+  }
+}
+
+// The Gamma tables of a launch (P.gam_shared): workgroup b stages the y of
+// slot b as the stem kernel does and writes its table P.gam + b gam_doubles
+// and sums P.kap_y + b n_gam.  Runs ahead of sk_dag_stem_kernel, which is
+// ordered behind it: the kernel boundary makes the tables visible to every
+// workgroup.
+template <int MAXK>
+__global__ void __launch_bounds__(64 * StemWaves<MAXK>::value) sk_gamma_table_kernel(StemLaunch P) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int nwaves = blockDim.x >> 6;
+  const int slot = blockIdx.x;
+  if (slot >= P.n_slots) return;  // (the whole workgroup, ahead of every barrier)
+  const StemLds L = stem_lds_carve<MAXK>(P, nwaves);
+  for (int k = threadIdx.x; k < 256; k += blockDim.x) L.co[k] = P.co_subst[k];
+  for (int k = threadIdx.x; k < P.n_gpow; k += blockDim.x) L.gp[k] = P.gpow[k];
+  lds_f64* R = L.Rall + (size_t)wave * P.lds_max_nl;
+  const int wave_u = __builtin_amdgcn_readfirstlane(wave);
+  // stage_y reads gp (the slot weights of the narrow classes) before its
+  // first barrier, as it may in the stem kernel, whose item loop opens with one
+  __syncthreads();
+  YView Y;
+  stage_y<MAXK>(P, L, P.slot_y[slot], Y);
+  gamma_rows<MAXK>(P, Y, R, L.co, L.gp, P.gam + (size_t)slot * P.gam_doubles,
+                   P.kap_y + (size_t)slot * P.xset.n_gam, wave_u, nwaves, lane);
+}
+
+template <int MAXK>
+__global__ void __launch_bounds__(64 * StemWaves<MAXK>::value) sk_dag_stem_kernel(StemLaunch P) {
+  const DevSet& s = P.yset;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int nwaves = blockDim.x >> 6;
+  const int maxnl = P.lds_max_nl;  // multiple of 64
+  constexpr int PW = pass_width<MAXK>();
+
+  const StemLds L = stem_lds_carve<MAXK>(P, nwaves);
+  lds_f64* co = L.co;
+  lds_f64* gp = L.gp;
+  lds_i32* ctl = L.ctl;
+  lds_f64* kap = L.kap;
+
+  for (int k = threadIdx.x; k < 256; k += blockDim.x) co[k] = P.co_subst[k];
+  for (int k = threadIdx.x; k < P.n_gpow; k += blockDim.x) gp[k] = P.gpow[k];
+
+  lds_f64* R = L.Rall + (size_t)wave * maxnl;
+  lds_f64* hb = L.hball + (size_t)wave * 64 * PW;
+  for (int j = 0; j < PW; ++j) hb[64 * j + lane] = 0.0;  // kept zero between MATCH passes
+  double* slab = P.scratch + (size_t)(blockIdx.x * nwaves + wave) * P.slab_doubles;
+  // the workgroup's Phi table: n_phi rows of 64*MAXK, then their sums kappa
+  double* phitab = P.phi_on ? P.phi + (size_t)blockIdx.x * P.phi_doubles : nullptr;
+  double* phikap = P.phi_on ? phitab + (size_t)P.xset.n_phi * (64 * MAXK) : nullptr;
+  const int band = (int)P.band;
+
+  // wave index as an SGPR value: every branch below on it is wave-uniform
+  const int wave_u = __builtin_amdgcn_readfirstlane(wave);
+  for (;;) {
+    __syncthreads();
+    if (threadIdx.x == 0) ctl[0] = atomicAdd(P.item_counter, 1);
+    __syncthreads();
+    const int it = __builtin_amdgcn_readfirstlane(ctl[0]);
+    if (it >= P.n_items) break;
+    const int4 item = P.items[it];  // {y, base, count, Gamma table slot}
+    const int y = item.x;
+    YView Y;
+    stage_y<MAXK>(P, L, y, Y);
+    const int nb = Y.nb, bb = Y.bb;
+
+    // Gamma rows of this y (gapless y only): the y's shared table, built by
+    // sk_gamma_table_kernel (its sums kappa into LDS), or this workgroup's
+    // own, built here
     const bool gam = P.gam_on && s.ex_gapless[y];
+    double* gamtab = nullptr;
     if (gam) {
       const DevSet& xset = P.xset;
-      for (int g = wave_u; g < xset.n_gam; g += nwaves) {
-        const uint32_t key = xset.gam_key[g];
-        const int gcode = (int)(key >> 16) * 16, glen = (int)(key & 0xffff);
-        double kp = 0.0;
-        for (int k = 0; k < MAXK; ++k) {
-          const int q = lane + 64 * k;
-          double M = 0.0;
-          if (q < Y.nl) {
-            const uint4 nd = Y.nrg[q];
-            const int ylen = (int)(s.yn_b[nb + q] & 0xffff);
-            if (((nd.x >> 16) & 0xff) == 0 && (band == 0 || abs(glen - ylen) <= band)) {
-              double vs;
-              if ((nd.y >> 24) != 0u) {
-                vs = co[gcode + ((nd.y >> 16) & 0xf)] * (double)__uint_as_float(nd.w);
-              } else {
-                vs = 0.0;
-                const int yb0 = (int)(s.yn_b[nb + q] >> 16), ynb = (int)(nd.x >> 24);
-                for (int b = 0; b < ynb; ++b)
-                  vs += co[gcode + s.bpf_code[bb + yb0 + b]] * (double)s.bpf_p[bb + yb0 + b];
-              }
-              M = vs * gp[nd.y & 0xffff];
-              kp += M * s.yn_P[nb + q];
-            }
-          }
-          R[q] = M;
-        }
-        for (int off = 32; off > 0; off >>= 1) kp += __shfl_xor(kp, off, 64);
-        if (lane == 0) kap[g] = kp;
-        wave_sync();
-        int c0 = 0;
-        if (band > 0) c0 = Y.ycs[min(max(glen - band, 0), Y.lmax + 1)];
-        c0 = __builtin_amdgcn_readfirstlane(c0);
-        if (c0 < Y.nch) iy_sweep<node_weights<MAXK>(), node_weights_f32<MAXK>()>(Y, R, c0, lane);
-        double* grow = gamtab + (size_t)g * (64 * MAXK);
-        for (int k = 0; k < MAXK; ++k)
-          if (lane + 64 * k < Y.nl) grow[lane + 64 * k] = R[lane + 64 * k];  // (the tail is never read)
-        wave_sync();
+      if (P.gam_shared) {
+        gamtab = P.gam + (size_t)item.w * P.gam_doubles;
+        const double* __restrict__ ky = P.kap_y + (size_t)item.w * xset.n_gam;
+        for (int g = threadIdx.x; g < xset.n_gam; g += blockDim.x) kap[g] = ky[g];
+      } else {
+        gamtab = P.gam + (size_t)blockIdx.x * P.gam_doubles;
+        gamma_rows<MAXK>(P, Y, R, co, gp, gamtab, kap, wave_u, nwaves, lane);
       }
       __syncthreads();  // the table and kappa, for every wave's pairs
 
@@ -1283,6 +1385,26 @@ hipError_t launch_stem(const StemLaunch& P, int grid, int nwaves, hipStream_t st
   case K:                                                                                  \
     hipLaunchKernelGGL(sk_dag_stem_kernel<K>, dim3(grid), dim3(64 * nwaves), lds, st, P); \
     break;
+    SK_STEM_CLASSES(SK_CASE)
+#undef SK_CASE
+    default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_gamma_tables(const StemLaunch& P, int nwaves, hipStream_t st) {
+  if (!P.gam_shared || P.n_slots <= 0) return hipSuccess;
+  const size_t lds = stem_lds_bytes(P, nwaves);
+  const int maxk = stem_maxk(P.lds_max_nl);
+  switch (maxk) {
+#define SK_CASE(K)                                                                                  \
+  case K: {                                                                                        \
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(sk_gamma_table_kernel<K>),    \
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);      \
+    if (e != hipSuccess) return e;                                                                 \
+    hipLaunchKernelGGL(sk_gamma_table_kernel<K>, dim3(P.n_slots), dim3(64 * nwaves), lds, st, P); \
+    break;                                                                                         \
+  }
     SK_STEM_CLASSES(SK_CASE)
 #undef SK_CASE
     default: return hipErrorInvalidValue;

@@ -22,8 +22,8 @@ struct StemLaunch {
   // LDS sizing (maxima over the y examples of this launch)
   int32_t lds_max_nl = 0, lds_max_edges = 0, lds_max_bpf = 0, lds_max_nch = 0;
   int32_t lds_max_len_pad = 0;  // length -> first node table (max node length + 2, padded)
-  // work: items {y, base, count, 0}; pair t of an item is x = xs[base+t],
-  // result -> out[oidx[base+t]]
+  // work: items {y, base, count, slot}; pair t of an item is x = xs[base+t],
+  // result -> out[oidx[base+t]]; slot = the y's Gamma table (gam_shared)
   const int4* items = nullptr;
   int32_t n_items = 0;
   const int32_t* xs = nullptr;
@@ -32,11 +32,19 @@ struct StemLaunch {
   int* item_counter = nullptr;
   double* scratch = nullptr;   // per-wave G0 slabs
   int64_t slab_doubles = 0;
-  // Gamma rows (gam_on: the x set has gamma keys): per-workgroup table of
-  // xset.n_gam rows of 64*MAXK doubles, Gamma_g(y) of the current item's y
+  // Gamma rows (gam_on: the x set has gamma keys): tables of xset.n_gam rows
+  // of 64*MAXK doubles, Gamma_g(y).  gam_shared: one table per gapless y of
+  // the launch (table `slot` of gam; its sums kappa_g in kap_y), written by
+  // sk_gamma_table_kernel ahead of the stem kernel (launch_gamma_tables: one
+  // workgroup per slot, y = slot_y[slot]) and read by every workgroup on that
+  // y.  Else one table per workgroup, rebuilt for every item's y.
   double* gam = nullptr;
-  int64_t gam_doubles = 0;  // per workgroup
+  int64_t gam_doubles = 0;  // per table
   int32_t gam_on = 0;
+  int32_t gam_shared = 0;
+  double* kap_y = nullptr;            // n_slots x xset.n_gam (gam_shared)
+  const int32_t* slot_y = nullptr;    // n_slots (device; gam_shared)
+  int32_t n_slots = 0;
   // Phi rows (phi_on: the x set has phi keys): per-workgroup table of
   // xset.n_phi rows of 64*MAXK doubles and their n_phi sums; the item's phi
   // keys item_phi[item_phi_off[it] .. item_phi_off[it + 1])
@@ -391,6 +399,11 @@ hipError_t launch_prep(const DevSet& s, const DevParamNodes& pn, const double* g
                        hipStream_t st);
 size_t stem_lds_bytes(const StemLaunch& P, int nwaves);
 hipError_t launch_stem(const StemLaunch& P, int grid, int nwaves, hipStream_t st);
+// the launch's shared Gamma tables (P.gam_shared): P.n_slots workgroups of the
+// stem kernel's shape, on a stream the stem launch that reads them is ordered
+// behind (sk_api.cpp: all classes' tables first, ahead of the stem launches
+// and of the string kernel's side stream)
+hipError_t launch_gamma_tables(const StemLaunch& P, int nwaves, hipStream_t st);
 hipError_t stem_kernel_attr(int max_nl, int* max_dyn_lds, int* vgprs, int* max_waves);
 int stem_maxk(int max_nl);
 

@@ -324,6 +324,7 @@ struct sk_context {
   // bit MAXK/4 per DAG stem register class; bit log2(CPL) (+4 when banded)
   // per 4-D stem class
   uint32_t last_stem_classes = 0, last_s4d_classes = 0;
+  int32_t last_gamma_shared = 0;  // class launches of the last call that read shared Gamma tables
   // RCCL communicator of sk_comm_init (ncclComm_t, csrc/host/shard.cpp)
   void* comm = nullptr;
 };
@@ -2355,6 +2356,7 @@ int run_pairs(sk_context* ctx, sk_dataset* xs_, sk_dataset* ys_, const sk_kernel
   ctx->last_launches = 0;
   sk::lev_reset(ctx);
   ctx->last_stem_classes = ctx->last_s4d_classes = 0;
+  ctx->last_gamma_shared = 0;
   if (n == 0) return SK_OK;
   const int nx = (int)xs_->ex.size(), ny = (int)ys_->ex.size();
   for (int64_t k = 0; k < n; ++k)
@@ -2395,9 +2397,13 @@ int run_pairs(sk_context* ctx, sk_dataset* xs_, sk_dataset* ys_, const sk_kernel
     int max_nl = 0, max_edges = 0, max_bpf = 0, max_nch = 0;
     int nwaves = 1, grid = 1;
     size_t item_off = 0, n_items = 0;
+    size_t slot_off = 0, n_slots = 0;         // the class's Gamma table slots in slot_y
+    bool gam_shared = false;                  // one Gamma table per y (else per workgroup)
+    size_t tab_off = 0;                       // its tables in the scratch's table region (doubles)
   };
   std::vector<StemClass> classes;
   std::vector<int4> items;
+  std::vector<int32_t> slot_y;  // Gamma table slot -> y, class by class
   std::vector<int32_t> ixs;
   std::vector<int64_t> ioidx;
   std::vector<int32_t> big_x, big_y;  // pairs whose y goes to the big-y kernel
@@ -2471,6 +2477,7 @@ int run_pairs(sk_context* ctx, sk_dataset* xs_, sk_dataset* ys_, const sk_kernel
     for (int maxk : {32, 28, 24, 20, 17, 16, 12, 8, 4}) {
       StemClass C;
       C.maxk = maxk;
+      C.slot_off = slot_y.size();
       bool any = false;
       for (int j = 0; j < ny; ++j) {
         if (cnt[j + 1] == cnt[j] || !in_class(j, maxk)) continue;
@@ -2526,6 +2533,8 @@ int run_pairs(sk_context* ctx, sk_dataset* xs_, sk_dataset* ys_, const sk_kernel
       // (few boundaries) and the last ones a round each (short launch tail).
       // Items are pulled in this order (K = 1.5; NS 161k pairs/s at K = 1,
       // 160.8k at 1.5, 160.0k at 2, 157.2k at 8; C2 148k at 1.5, 140k at 1).
+      // A gapless y of a launch with gamma keys gets a Gamma table slot,
+      // carried in its items' .w (-1: none).
       std::vector<int> ysel;
       double class_cost = 0.0;
       for (int j = 0; j < ny; ++j) {
@@ -2544,6 +2553,11 @@ int run_pairs(sk_context* ctx, sk_dataset* xs_, sk_dataset* ys_, const sk_kernel
       C.item_off = items.size();
       for (int j : ysel) {
         const double yw = (double)PY.ex_nl[j];
+        int slot = -1;
+        if (L.gam_on && PY.ex_gapless[j]) {
+          slot = (int)(slot_y.size() - C.slot_off);
+          slot_y.push_back(j);
+        }
         int64_t b = cnt[j];
         while (b < cnt[j + 1]) {
           const double target = remaining * share;
@@ -2555,11 +2569,12 @@ int run_pairs(sk_context* ctx, sk_dataset* xs_, sk_dataset* ys_, const sk_kernel
             for (int64_t t = e; t < re; ++t) cost += (double)PX.ex_nl[x[byy[t]]] * yw;
             e = re;
           }
-          items.push_back(make_int4(j, (int)b, (int)(e - b), 0));
+          items.push_back(make_int4(j, (int)b, (int)(e - b), slot));
           remaining -= cost;
           b = e;
         }
       }
+      C.n_slots = slot_y.size() - C.slot_off;
       C.n_items = items.size() - C.item_off;
       C.grid = (int)std::min<int64_t>(C.grid, std::max<int64_t>(1, (int64_t)C.n_items));
       classes.push_back(C);
@@ -2656,6 +2671,7 @@ int run_pairs(sk_context* ctx, sk_dataset* xs_, sk_dataset* ys_, const sk_kernel
   need += 256 * 8 + 16 * 8 + (size_t)(max_len + 4) * 8 * 2;
   need += 1024;
   need += items.size() * sizeof(int4) + nb * (4 + 8) + nb * 8 * 2 + nb * 4 * 2 + 64 + 8 * 256;
+  need += slot_y.size() * 4 + 256;
   need += big_x.size() * (4 + 4 + 8) + 3 * 256;
   need += 16 * 256;
   rc = ensure_work(ctx, need);
@@ -2673,6 +2689,7 @@ int run_pairs(sk_context* ctx, sk_dataset* xs_, sk_dataset* ys_, const sk_kernel
   int32_t* d_px = A.take<int32_t>(nb);
   int32_t* d_py = A.take<int32_t>(nb);
   int* d_ctr = A.take<int>(64);
+  int32_t* d_sloty = A.take<int32_t>(std::max<size_t>(slot_y.size(), 1));
   int32_t* d_bx = A.take<int32_t>(std::max<size_t>(big_x.size(), 1));
   int32_t* d_by = A.take<int32_t>(std::max<size_t>(big_x.size(), 1));
   int64_t* d_bo = A.take<int64_t>(std::max<size_t>(big_x.size(), 1));
@@ -2720,6 +2737,7 @@ int run_pairs(sk_context* ctx, sk_dataset* xs_, sk_dataset* ys_, const sk_kernel
     SK_HIP(ctx, sk::h2d(ctx, d_items, items.data(), items.size() * sizeof(int4), S));
     SK_HIP(ctx, sk::h2d(ctx, d_ixs, ixs.data(), nb * 4, S));
     SK_HIP(ctx, sk::h2d(ctx, d_oidx, ioidx.data(), nb * 8, S));
+    SK_HIP(ctx, sk::h2d(ctx, d_sloty, slot_y.data(), slot_y.size() * 4, S));
     if (phi_on) {
       SK_HIP(ctx, sk::h2d(ctx, d_iphi_off, item_phi_off.data(), item_phi_off.size() * 4, S));
       if (!item_phi.empty())
@@ -2755,17 +2773,47 @@ int run_pairs(sk_context* ctx, sk_dataset* xs_, sk_dataset* ys_, const sk_kernel
     // one scratch region per stream, serving its classes in turn
     const bool two_streams = classes.size() > 1 && !SK_KNOB("SK_SERIAL_CLASSES");
     size_t scratch_need = 0, scratch_x = 0;
-    for (size_t c = 0; c < classes.size(); ++c) {
-      const StemClass& C = classes[c];
-      // + one junk row: root rows are stored there (never read)
-      const int64_t slab = (int64_t)(PX.max_slots + 1) * 64 * C.maxk;
-      // + the workgroups' Gamma tables
-      const int64_t gtab = (int64_t)PX.gam_key.size() * 64 * C.maxk;
-      // + their Phi tables and sums
-      const int64_t ptab = phi_on ? (int64_t)PX.phi_al.size() * (64 * C.maxk + 1) : 0;
-      const size_t b = (size_t)C.grid * (C.nwaves * slab + gtab + ptab) * sizeof(double);
-      size_t& r = (two_streams && (c & 1)) ? scratch_x : scratch_need;
-      r = std::max(r, b);
+    // The Gamma tables of a class launch: one per gapless y of the launch,
+    // written by the table kernel and read by every workgroup on that y, if
+    // the tables of the call's classes so far and this one's fit a budget
+    // taken from free memory (a quarter of it, the scratch held so far
+    // counted as free, 8 GiB at most; SK_GAM_TABLE_MB: the budget in MB, 0 =
+    // never); else one per workgroup, rebuilt per item.  The table kernels of
+    // all classes run first (below), so every class has table memory of its
+    // own, past the two streams' regions.  Free memory is asked for only
+    // when the tables do not fit the scratch the context already holds, and
+    // if the scratch cannot be had with them, the call goes on without
+    // (below).
+    size_t tab_total = 0;
+    auto size_classes = [&](size_t gam_budget) {
+      scratch_need = scratch_x = tab_total = 0;
+      for (size_t c = 0; c < classes.size(); ++c) {
+        StemClass& C = classes[c];
+        // + one junk row: root rows are stored there (never read)
+        const int64_t slab = (int64_t)(PX.max_slots + 1) * 64 * C.maxk;
+        // + the Gamma tables: per y of the launch (and their sums), or per workgroup
+        const int64_t gtab1 = (int64_t)PX.gam_key.size() * 64 * C.maxk;
+        const size_t shared_b = C.n_slots * (size_t)(gtab1 + (int64_t)PX.gam_key.size()) * sizeof(double);
+        C.gam_shared = C.n_slots > 0 && tab_total + shared_b <= gam_budget;
+        if (C.gam_shared) {
+          C.tab_off = tab_total / sizeof(double);
+          tab_total += shared_b;
+        }
+        // + their Phi tables and sums
+        const int64_t ptab = phi_on ? (int64_t)PX.phi_al.size() * (64 * C.maxk + 1) : 0;
+        const size_t b = (size_t)C.grid * (C.nwaves * slab + ptab + (C.gam_shared ? 0 : gtab1)) * sizeof(double);
+        size_t& r = (two_streams && (c & 1)) ? scratch_x : scratch_need;
+        r = std::max(r, b);
+      }
+    };
+    const bool any_slots = !PX.gam_key.empty() && !slot_y.empty();
+    size_classes(any_slots ? SIZE_MAX : 0);
+    if (const char* e = SK_KNOB("SK_GAM_TABLE_MB")) {
+      size_classes((size_t)std::max(0.0, std::atof(e) * 1048576.0));
+    } else if (tab_total > 0 && scratch_need + scratch_x + tab_total + 512 > ctx->scratch_bytes) {
+      size_t free_b = 0, total_b = 0;
+      SK_HIP(ctx, hipMemGetInfo(&free_b, &total_b));
+      size_classes(std::min<size_t>((free_b + ctx->scratch_bytes) / 4, (size_t)8 << 30));
     }
     // big-y kernel: per wave S, G1 and the G0 slots, rows of `big_stride`
     // doubles; as many waves as pairs, the grid, and a scratch budget allow
@@ -2783,10 +2831,21 @@ int run_pairs(sk_context* ctx, sk_dataset* xs_, sk_dataset* ys_, const sk_kernel
       scratch_need = std::max(scratch_need,
                               (size_t)big_grid * sk::kStemBigWaves * (size_t)big_wave * sizeof(double));
     }
-    scratch_need = (scratch_need + 255) / 256 * 256;
-    rc = ensure_scratch(ctx, std::max<size_t>(scratch_need + scratch_x, 64));
+    const size_t big_need = scratch_need;  // (>= the classes' need on the main stream)
+    auto get_scratch = [&]() {
+      scratch_need = (std::max(scratch_need, big_need) + 255) / 256 * 256;
+      scratch_x = (scratch_x + 255) / 256 * 256;
+      return ensure_scratch(ctx, std::max<size_t>(scratch_need + scratch_x + tab_total, 64));
+    };
+    rc = get_scratch();
+    if (rc && tab_total > 0) {  // not with the shared tables: per-workgroup tables then
+      (void)hipGetLastError();
+      size_classes(0);
+      rc = get_scratch();
+    }
     if (rc) return rc;
     double* scratch_cls = ctx->scratch + scratch_need / sizeof(double);
+    double* scratch_tab = scratch_cls + scratch_x / sizeof(double);
 #ifdef SK_STAMPS
     unsigned long long* d_stamps = nullptr;
     SK_HIP(ctx, hipMalloc(&d_stamps, 16 * sizeof(unsigned long long)));
@@ -2796,14 +2855,11 @@ int run_pairs(sk_context* ctx, sk_dataset* xs_, sk_dataset* ys_, const sk_kernel
       std::fprintf(stderr, "[host] pairs=%lld plan %.2f ms, phi keys %.2f ms, uploads+prep %.2f ms\n",
                    (long long)n, th1 - th0, th2 - th1, now_ms() - th2);
     SK_HIP(ctx, hipEventRecord(ctx->ev0, S));
-    if (two_streams) {
-      SK_HIP(ctx, hipEventRecord(ctx->evk, S));
-      SK_HIP(ctx, hipStreamWaitEvent(ctx->cls, ctx->evk, 0));
-    }
+    std::vector<sk::StemLaunch> launches(classes.size());
     for (size_t c = 0; c < classes.size(); ++c) {
       const StemClass& C = classes[c];
       const bool on_cls = two_streams && (c & 1);
-      sk::StemLaunch SL;
+      sk::StemLaunch& SL = launches[c];
       SL.xset = xs_->dev;
       SL.yset = ys_->dev;
       SL.pn = pn;
@@ -2828,18 +2884,50 @@ int run_pairs(sk_context* ctx, sk_dataset* xs_, sk_dataset* ys_, const sk_kernel
       SL.scratch = on_cls ? scratch_cls : ctx->scratch;
       SL.gam_on = !PX.gam_key.empty();
       SL.gam_doubles = (int64_t)PX.gam_key.size() * SL.lds_max_nl;
-      SL.gam = SL.scratch + (size_t)C.grid * C.nwaves * SL.slab_doubles;
+      // the workgroups' region: slabs, Gamma tables (unless shared), Phi tables
+      double* wg_tab = SL.scratch + (size_t)C.grid * C.nwaves * SL.slab_doubles;
+      SL.gam_shared = C.gam_shared ? 1 : 0;
+      SL.n_slots = C.gam_shared ? (int32_t)C.n_slots : 0;
+      SL.slot_y = d_sloty + C.slot_off;
+      SL.gam = C.gam_shared ? scratch_tab + C.tab_off : wg_tab;
+      SL.kap_y = SL.gam + C.n_slots * (size_t)SL.gam_doubles;  // (gam_shared: past the class's tables)
       SL.phi_on = phi_on ? 1 : 0;
       SL.phi_doubles = phi_on ? (int64_t)PX.phi_al.size() * (SL.lds_max_nl + 1) : 0;
-      SL.phi = SL.gam + (size_t)C.grid * SL.gam_doubles;
+      SL.phi = wg_tab + (C.gam_shared ? 0 : (size_t)C.grid * SL.gam_doubles);
       SL.item_phi_off = d_iphi_off + C.item_off;
       SL.item_phi = d_iphi;
 #ifdef SK_STAMPS
       SL.stamps = d_stamps;
 #endif
+    }
+    // Every class's Gamma tables first (0.2 ms each on a free GPU), ahead of
+    // the stem launches of both streams and of the string kernel on the side
+    // stream.  A table kernel's workgroups need a stem workgroup's LDS: behind
+    // a running persistent launch (another class's, or the string kernel,
+    // 50 ms per NS step) they would wait for it to end, and the stem launch
+    // behind them with it, instead of filling the GPU as its workgroups retire.
+    // The side stream forked at evf, ahead of the stem uploads; waiting for
+    // evk as well, its string kernel now also starts behind those uploads
+    // (≈ 1 ms per NS step) and, on the first call of a dataset and loop_gap,
+    // behind sk_prep_kernel (≈ 20 ms, once).  The table kernels stand outside
+    // the class launches' event brackets: sk_last_launch_ms does not count
+    // them (0.5 ms per NS step); the stem span (ev0 .. ev1) does.
+    bool any_tables = false;
+    for (size_t c = 0; c < classes.size(); ++c) {
+      SK_HIP(ctx, sk::launch_gamma_tables(launches[c], classes[c].nwaves, S));
+      any_tables = any_tables || classes[c].gam_shared;
+    }
+    if (two_streams || (side && any_tables)) SK_HIP(ctx, hipEventRecord(ctx->evk, S));
+    if (two_streams) SK_HIP(ctx, hipStreamWaitEvent(ctx->cls, ctx->evk, 0));
+    if (side && any_tables) SK_HIP(ctx, hipStreamWaitEvent(ctx->side, ctx->evk, 0));
+    for (size_t c = 0; c < classes.size(); ++c) {
+      const StemClass& C = classes[c];
+      const bool on_cls = two_streams && (c & 1);
+      const sk::StemLaunch& SL = launches[c];
       SK_HIP(ctx, sk::lev_mark(ctx, on_cls ? ctx->cls : S));
       SK_HIP(ctx, sk::launch_stem(SL, C.grid, C.nwaves, on_cls ? ctx->cls : S));
       SK_HIP(ctx, sk::lev_mark(ctx, on_cls ? ctx->cls : S));
+      if (C.gam_shared) ++ctx->last_gamma_shared;
       ctx->last_stem_classes |= 1u << (C.maxk % 4 ? C.maxk : C.maxk / 4);  // (MAXK 17: bit 17)
     }
     if (two_streams) {
@@ -4490,6 +4578,8 @@ int sk_last_classes(const sk_context* ctx, uint32_t* stem_maxk_mask, uint32_t* s
   if (stem4d_mask) *stem4d_mask = ctx->last_s4d_classes;
   return SK_OK;
 }
+
+int32_t sk_last_gamma_shared(const sk_context* ctx) { return ctx ? ctx->last_gamma_shared : 0; }
 
 void sk_ribosum_tables(float* s16, float* p256) {
   if (s16) std::memcpy(s16, SK_RIBOSUM_S, sizeof(SK_RIBOSUM_S));

@@ -745,6 +745,12 @@ class Context:
         col = sorted(1 << (k & 3) for k in range(8, 12) if b.value >> k & 1)
         return dict(stem_maxk=maxk, stem4d=s4d, stem4d_col=col)
 
+    def last_gamma_shared(self) -> int:
+        """sk_last_gamma_shared: the class launches of the last compute call
+        that read one Gamma table per y, built by the table kernel (the others
+        built a table per workgroup and work item)."""
+        return int(lib().sk_last_gamma_shared(self._h))
+
 
 def stem4d_col_shape(min_len: int, max_len: int) -> dict:
     """Shape of the column-pipelined 4-D kernel for a batch of y examples of

@@ -28,7 +28,8 @@ timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $ROOT/$OUT/prof -o run --o
 echo trace_done
 run_pmc() {  # name counters...
   local name=$1; shift
-  timeout -s KILL 300 rocprofv3 --pmc "$@" -d $ROOT/$OUT/$name -o run --output-format csv -- \
+  # (SK_PACK_STATS: the schedule's host-counted row transfers into the log, for profile_summary.py)
+  SK_PACK_STATS=1 timeout -s KILL 300 rocprofv3 --pmc "$@" -d $ROOT/$OUT/$name -o run --output-format csv -- \
     python3 $ROOT/bench.py --config $CFG --steps 1 --warmup 0 --no-cpu-baseline > $OUT/$name.log 2>&1 || { tail -20 $OUT/$name.log; return 1; }
   echo ${name}_done
 }

@@ -48,6 +48,35 @@ def bench_line(path):
     return line
 
 
+def schedule_rows(path, line):
+    """The DAG stem schedule's row transfers as the host counts them when the
+    x set is packed (the "[sk pack] gamma schedule:" line SK_PACK_STATS=1
+    prints, here in a bench log), in bytes per cell: 8 B x transfers of a
+    category per example / non-leaf x nodes per example (every pair of an x
+    repeats its transfers at its y's row length).  The non-leaf nodes per
+    example are taken as sqrt(cells per pair) of the bench line -- a Gram's x
+    and y are of one set; NS: 1,015 against the set's 1,014.  The counter's
+    bytes fall below the sum by what L2 serves."""
+    import re
+    m = None
+    for ln in open(path, errors="replace"):
+        m = re.search(r"gamma schedule: (\d+) nodes, (\d+) rows, (\d+) unstored, (\d+) slots; stored (\d+), "
+                      r"reads: slab (\d+) gamma (\d+) phi (\d+), from registers (\d+)", ln) or m
+    if m is None:
+        return None
+    nodes, rows, unstored, slots, stored, slab, gam, phi, reg = (int(v) for v in m.groups())
+    per = {"stored_rows_written": stored, "slab_rows_read": slab, "gamma_rows_read": gam, "phi_rows_read": phi}
+    n_ex = line["config"]["n_sequences"]
+    nl = (line["cells_per_step"] / line["config"]["pairs_per_step_per_gpu"]) ** 0.5
+    out = {"examples": n_ex, "x_nodes": nodes, "x_rows": rows, "rows_from_registers": reg,
+           "row_transfers": per, "non_leaf_nodes_per_example": nl,
+           "bytes_per_cell": {k: 8.0 * v / n_ex / nl for k, v in per.items()},
+           "source": "host count of the packed x schedule (SK_PACK_STATS=1), 8 B x transfers per example / "
+                     "non-leaf x nodes per example"}
+    out["bytes_per_cell"]["sum"] = sum(out["bytes_per_cell"].values())
+    return out
+
+
 def pmc(d, ksub):
     tot, disp = {}, set()
     for f in glob.glob(os.path.join(d, "**", "*counter_collection.csv"), recursive=True):
@@ -114,6 +143,10 @@ def main():
            "pmc_dispatches": {"FETCH_SIZE": f["dispatches"], "WRITE_SIZE": w["dispatches"]},
            "source": f"rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes) -- bench.py --config {cfg} "
                      f"--steps 1 --warmup 0 --no-cpu-baseline; kernels matching '{ksub}'"}
+    if "dag_stem" in ksub:
+        sched = schedule_rows(os.path.join(out, "FETCH_SIZE.log"), fl)
+        if sched:
+            res["schedule_rows"] = sched
     ldsd = os.path.join(out, "LDS")
     if os.path.isdir(ldsd):
         c = pmc(ldsd, ksub)
