@@ -1,5 +1,5 @@
 """ctypes loader for the CPU ORACLE (oracle/liboracle.so) and the partial
-reference build (oracle/_ref/libskref.so).
+reference builds (oracle/_ref/libskref.so and libskref_{lite,4d,str,bpla}.so).
 
 TEST INFRASTRUCTURE ONLY: imported by tests/, __graft_entry__.smoke() and
 bench.py's cpu_baseline leg, always as the checker, never as the product.
@@ -102,6 +102,220 @@ def reference_partial():
     return _r
 
 
+# ------------------------------------------------ the reference's own DP code
+# oracle/_ref/libskref_{lite,4d,str,bpla}.so: the reference's DP translation
+# units compiled in place by oracle/Makefile, one library per reference tool.
+REF_DP_SOS = {k: os.path.join(HERE, "_ref", f"libskref_{k}.so") for k in ("lite", "4d", "str", "bpla")}
+_rdp = {}
+_P = C.c_void_p
+
+
+def _bind_lite(L):
+    L.skl_data_new.restype = _P
+    L.skl_data_new.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.POINTER(_D), _D, C.c_float, C.c_int]
+    L.skl_data_free.argtypes = [_P]
+    for n in ("skl_n_nodes", "skl_seq_len", "skl_n_weight", "skl_n_roots", "skl_n_edges",
+              "skl_n_bpfreq"):
+        getattr(L, n).argtypes = [_P]
+        getattr(L, n).restype = C.c_int
+    L.skl_nodes.argtypes = [_P, _U, _U, _U, _U, _F, _U]
+    L.skl_edges.argtypes = [_P, _U, _U]
+    L.skl_bpfreq.argtypes = [_P, _U, _F]
+    L.skl_roots.argtypes = [_P, _U]
+    L.skl_weight.argtypes = [_P, _F]
+    L.skl_kernel.restype = C.c_double
+    L.skl_kernel.argtypes = [C.c_int, _P, _P, _D, C.c_uint]
+
+
+def _bind_4d(L):
+    L.sk4_kernel.restype = C.c_double
+    L.sk4_kernel.argtypes = [C.c_char_p, _D, C.c_char_p, _D, C.c_double, C.c_double, C.c_double,
+                             C.c_float, C.c_int, C.c_uint, C.c_uint, C.c_float]
+    L.sk4_phmm_posterior.argtypes = [C.c_char_p, C.c_char_p, _D]
+    L.sk4_alignment_constraints.argtypes = [C.c_char_p, C.c_char_p, C.c_float, C.c_uint, _U, _U]
+
+
+def _bind_str(L):
+    L.sks_kernel.restype = C.c_double
+    L.sks_kernel.argtypes = [C.c_char_p, C.c_char_p, C.c_double]
+
+
+def _bind_bpla(L):
+    L.skb_data_new.restype = _P
+    L.skb_data_new.argtypes = [C.c_int, C.POINTER(C.c_char_p), _D, C.c_int]
+    L.skb_data_free.argtypes = [_P]
+    L.skb_seq_len.argtypes = [_P]
+    L.skb_seq_len.restype = C.c_int
+    L.skb_weights.argtypes = [_P, _F, _F, _F]
+    L.skb_kernel.restype = C.c_double
+    L.skb_kernel.argtypes = [_P, _P, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double,
+                             C.c_double, _D]
+    L.skb_gradients.restype = C.c_double
+    L.skb_gradients.argtypes = [_P, _P, C.c_double, C.c_double, C.c_double, C.c_double, _D, _D]
+
+
+def reference_dp(which: str):
+    """The reference's own DP code for one tool: 'lite' (stem_kernel_lite),
+    '4d' (stem_kernel with the PairHMM), 'str' (string_kernel) or 'bpla'
+    (bpla_kernel).  Raises if the library is missing or does not load."""
+    if which not in _rdp:
+        path = REF_DP_SOS[which]
+        if not os.path.exists(path):
+            raise RuntimeError(f"{path} not built (make -C oracle, with the reference present)")
+        L = C.CDLL(path)
+        {"lite": _bind_lite, "4d": _bind_4d, "str": _bind_str, "bpla": _bind_bpla}[which](L)
+        _rdp[which] = L
+    return _rdp[which]
+
+
+def reference_dp_expected() -> bool:
+    """True when the reference DP libraries must exist: the reference tree or
+    a built oracle/_ref is present (only with both absent may a test skip)."""
+    return os.path.isdir("/root/reference") or os.path.isdir(os.path.join(HERE, "_ref"))
+
+
+def _packed_ptr(b):
+    b = np.ascontiguousarray(b, dtype=np.float64)
+    if b.size == 0:
+        b = np.zeros(1)
+    return b
+
+
+class RMData:
+    """One example built by the reference's own Data constructor
+    (stem_kernel_lite/data.cpp) from injected base-pairing probabilities:
+    the per-row packed matrices the oracle takes, and the oracle's averaged
+    table (the averaging itself is not part of the reference build)."""
+
+    def __init__(self, rows: Sequence[str], bpp_rows, th=0.01, use_bp=True, avg=None):
+        L = reference_dp("lite")
+        n = len(rows)
+        self._rows = (C.c_char_p * n)(*[r.encode() for r in rows])
+        self._keep = []
+        barr = (_D * n)()
+        a = None
+        if use_bp:
+            for k, b in enumerate(bpp_rows):
+                b = _packed_ptr(b)
+                self._keep.append(b)
+                barr[k] = b.ctypes.data_as(_D)
+            if avg is None:
+                om = OMData(rows, bpp_rows, th)
+                sl = oracle().orc_mdata_seq_len(om.h)
+                avg = np.zeros(max(sl * (sl - 1) // 2, 1))
+                oracle().orc_mdata_bpp(om.h, avg.ctypes.data_as(_D))
+            a = _packed_ptr(avg)
+            self._keep.append(a)
+        self.h = _P(L.skl_data_new(n, self._rows, barr, a.ctypes.data_as(_D) if a is not None else None,
+                                   C.c_float(th), int(use_bp)))
+
+    def __del__(self):
+        if getattr(self, "h", None) and "lite" in _rdp:
+            _rdp["lite"].skl_data_free(self.h)
+            self.h = None
+
+    def dag(self) -> dict:
+        L = reference_dp("lite")
+        nn, ne, nb = L.skl_n_nodes(self.h), L.skl_n_edges(self.h), L.skl_n_bpfreq(self.h)
+        nr, nw = L.skl_n_roots(self.h), L.skl_n_weight(self.h)
+        u = lambda k: np.zeros(max(k, 1), np.uint32)
+        f = lambda k: np.zeros(max(k, 1), np.float32)
+        first, last, ned, nbf, mp = u(nn), u(nn), u(nn), u(nn), u(nn)
+        w = f(nn)
+        L.skl_nodes(self.h, *(a.ctypes.data_as(_U) for a in (first, last, ned, nbf)),
+                    w.ctypes.data_as(_F), mp.ctypes.data_as(_U))
+        to, gaps = u(ne), u(ne)
+        L.skl_edges(self.h, to.ctypes.data_as(_U), gaps.ctypes.data_as(_U))
+        code, p = u(nb), f(nb)
+        L.skl_bpfreq(self.h, code.ctypes.data_as(_U), p.ctypes.data_as(_F))
+        roots = u(nr)
+        L.skl_roots(self.h, roots.ctypes.data_as(_U))
+        pw = f(nw)
+        L.skl_weight(self.h, pw.ctypes.data_as(_F))
+        return dict(first=first[:nn], last=last[:nn], n_edges=ned[:nn], n_bpfreq=nbf[:nn],
+                    weight=w[:nn], max_pa=mp[:nn], edge_to=to[:ne], edge_gaps=gaps[:ne],
+                    bp_code=code[:nb], bp_p=p[:nb], roots=roots[:nr], pos_weight=pw[:nw])
+
+
+def ref_kernel_value(kind: int, x: RMData, y: RMData, p) -> float:
+    """K(x, y) of lite kind 0..7 by the reference's own kernel classes
+    (def_kernel.h); p is a KernelParams-like object."""
+    v = (C.c_double * 8)(p.loop_gap, p.beta, p.stack, p.covar, p.gap, p.alpha, p.match, p.mismatch)
+    return reference_dp("lite").skl_kernel(kind, x.h, y.h, v, int(p.len_band))
+
+
+def ref_naive_string(x: str, y: str, gap=0.8) -> float:
+    return reference_dp("str").sks_kernel(x.encode(), y.encode(), gap)
+
+
+def ref_stem4d(x: str, bpx, y: str, bpy, gap=0.8, stack=1.0, subst=0.5, bp_bound=0.0, model=0,
+               loop=3, band=0, ali_bound=0.0) -> float:
+    """The reference's StemKernel::operator() (stem_kernel/stem_kernel.h)."""
+    keep = [np.ascontiguousarray(b, dtype=np.float64) if b is not None else None for b in (bpx, bpy)]
+    px = keep[0].ctypes.data_as(_D) if keep[0] is not None and keep[0].size else None
+    py = keep[1].ctypes.data_as(_D) if keep[1] is not None and keep[1].size else None
+    return reference_dp("4d").sk4_kernel(x.encode(), px, y.encode(), py, gap, stack, subst,
+                                         bp_bound, model, loop, band, ali_bound)
+
+
+def ref_phmm_posterior(x: str, y: str) -> np.ndarray:
+    fb = np.zeros((3, len(x) + 1, len(y) + 1))
+    reference_dp("4d").sk4_phmm_posterior(x.encode(), y.encode(), fb.ctypes.data_as(_D))
+    return fb
+
+
+def ref_alignment_constraints(x: str, y: str, ali_bound: float, band=0):
+    lo = np.zeros(len(x) + 1, np.uint32)
+    hi = np.zeros(len(x) + 1, np.uint32)
+    reference_dp("4d").sk4_alignment_constraints(x.encode(), y.encode(), ali_bound, band,
+                                                 lo.ctypes.data_as(_U), hi.ctypes.data_as(_U))
+    return lo, hi
+
+
+class RBData:
+    """One BPLA example built by the reference's own Data constructor
+    (bpla_kernel/data.cpp: fill_weight) on the injected averaged table."""
+
+    def __init__(self, rows: Sequence[str], bpp_rows, use_bp=True):
+        L = reference_dp("bpla")
+        n = len(rows)
+        self._rows = (C.c_char_p * n)(*[r.encode() for r in rows])
+        a = None
+        if use_bp:
+            om = OMData(rows, bpp_rows, 0.01)
+            sl = oracle().orc_mdata_seq_len(om.h)
+            a = np.zeros(max(sl * (sl - 1) // 2, 1))
+            oracle().orc_mdata_bpp(om.h, a.ctypes.data_as(_D))
+        self._keep = a
+        self.h = _P(L.skb_data_new(n, self._rows, a.ctypes.data_as(_D) if a is not None else None,
+                                   int(use_bp)))
+
+    def __del__(self):
+        if getattr(self, "h", None) and "bpla" in _rdp:
+            _rdp["bpla"].skb_data_free(self.h)
+            self.h = None
+
+    def weights(self):
+        L = reference_dp("bpla")
+        n = L.skb_seq_len(self.h)
+        a = [np.zeros(max(n, 1), np.float32) for _ in range(3)]
+        L.skb_weights(self.h, *(v.ctypes.data_as(_F) for v in a))
+        return [v[:n] for v in a]
+
+
+def ref_bpla(x: RBData, y: RBData, no_bp: bool, sw: bool, gap, ext, alpha, beta, table16) -> float:
+    t = (C.c_double * 16)(*table16)
+    return reference_dp("bpla").skb_kernel(x.h, y.h, int(no_bp), int(sw), gap, ext, alpha, beta, t)
+
+
+def ref_bpla_gradients(x: RBData, y: RBData, alpha, beta, gap, ext, table16):
+    t = np.ascontiguousarray(table16, dtype=np.float64)
+    d = np.zeros(4)
+    v = reference_dp("bpla").skb_gradients(x.h, y.h, alpha, beta, gap, ext, t.ctypes.data_as(_D),
+                                           d.ctypes.data_as(_D))
+    return v, d
+
+
 class OMData:
     """Oracle MData (one example)."""
 
@@ -168,10 +382,16 @@ def si_str(x: OMData, y: OMData, gap=0.8, match=1.0, mismatch=0.8) -> float:
     return oracle().orc_profile_string(x.h, y.h, gap, 0, 0.0, match, mismatch)
 
 
+def _log(v: float) -> float:
+    """C's log, as LogKernel (conv_kernel.h) calls it: -inf at 0 (a pair with
+    an empty DAG), where math.log raises."""
+    import math
+    return math.log(v) if v > 0.0 else (-math.inf if v == 0.0 else math.nan)
+
+
 def kernel_value(kind: int, x: OMData, y: OMData, p) -> float:
     """Composite kernels of def_kernel.h / conv_kernel.h from the components;
     p is a KernelParams-like object (attribute access)."""
-    import math
     stem = lambda: su_stem(x, y, p.loop_gap, p.beta, p.len_band)
     if kind == 0:
         return stem()
@@ -186,14 +406,14 @@ def kernel_value(kind: int, x: OMData, y: OMData, p) -> float:
     if kind == 5:
         return si_stem(x, y, p.loop_gap, p.stack, p.covar, p.len_band) + si_str(x, y, p.gap, p.match, p.mismatch)
     if kind == 6:
-        return p.beta * math.log(stem()) + 0.0
+        return p.beta * _log(stem()) + 0.0
     if 9 <= kind <= 12:
         return bpla(x, y, kind in (10, 12), kind in (11, 12), p.gap, p.ext, p.alpha, p.beta,
                     list(p.score_table))
     if kind == 8:
         raise ValueError("naive string kernel compares raw strings: use naive_string()")
     if kind == 7:
-        return (p.beta * math.log(stem()) + 0.0) + (p.alpha * math.log(su_str(x, y, p.gap, p.alpha)) + 0.0)
+        return (p.beta * _log(stem()) + 0.0) + (p.alpha * _log(su_str(x, y, p.gap, p.alpha)) + 0.0)
     raise ValueError(kind)
 
 

@@ -6,7 +6,9 @@
 // tests/test_oracle_pinning.py can pin the oracle's alphabet, IUPAC profile
 // and RIBOSUM85-60 restatements against the reference itself.
 // These are the only hot-path TUs that build with nothing but the C++
-// standard library; everything else needs Boost/ViennaRNA/config.h.
+// standard library; the DP TUs build against the stand-in headers of
+// standin/ (see sklite_shim.cpp, sk4d_shim.cpp, skstr_shim.cpp,
+// skbpla_shim.cpp).
 #include <cstring>
 #include <list>
 #include <string>

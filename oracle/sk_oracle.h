@@ -13,10 +13,13 @@
  *     (common/rna.cpp, common/profile.cpp, stem_kernel_lite/ribosum.cpp),
  *     compiled unmodified from /root/reference into oracle/_ref/ by
  *     oracle/Makefile and compared in tests/test_oracle_pinning.py;
- *   - the DAG builder and every kernel DP are "parity unpinned": the
- *     reference TUs that hold them need Boost, ViennaRNA and the
- *     configure-generated config.h, none of which exist in this image, and
- *     the reference ships no tests, fixtures or golden values.
+ *   - the DAG builder and every kernel DP are PINNED too: the reference TUs
+ *     that hold them are compiled unmodified and in place against the
+ *     stand-in Boost headers of oracle/ref_shim/standin/ into
+ *     oracle/_ref/libskref_{lite,4d,str,bpla}.so and compared, bit for bit,
+ *     in tests/test_oracle_dp_pinning.py;
+ *   - unpinned: ViennaRNA's folding, and the averaging of per-row matrices
+ *     into an alignment's matrix (common/bpmatrix.cpp, not compiled).
  */
 #ifndef SK_ORACLE_H
 #define SK_ORACLE_H

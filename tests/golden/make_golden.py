@@ -1,11 +1,12 @@
 """Generate tests/golden/*.npz: seeded inputs (sequences/alignments and their
 base-pairing matrices) with the oracle's kernel values.
 
-The reference cannot be built or run here (Boost/ViennaRNA/config.h absent,
-see DESIGN.md §Oracle) and ships no fixtures, so these vectors are produced by
+The reference's tools cannot be built or run here (Boost/ViennaRNA absent,
+see DESIGN.md §7) and it ships no fixtures, so these vectors are produced by
 the CPU oracle (oracle/sk_oracle.c).  They pin the oracle and the GPU engine
-against regressions; the oracle itself is pinned to the reference only for
-the alphabet/profile/RIBOSUM pieces (tests/test_oracle_pinning.py).
+against regressions; the oracle itself is pinned to the reference's own
+sources compiled in place: the alphabet/profile/RIBOSUM pieces
+(tests/test_oracle_pinning.py) and the DPs (tests/test_oracle_dp_pinning.py).
 
 Run:  python tests/golden/make_golden.py
 """

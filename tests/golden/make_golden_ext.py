@@ -3,10 +3,10 @@
 gradients (bpla_optimizer's per-pair step).
 
 Produced by the CPU oracle (oracle/sk_oracle.c) like lite_small.npz: the
-reference cannot be built here and ships no fixtures, so these pin the oracle
-and the GPU engine against regressions ("parity unpinned" against the
-reference's own output; the gradients are additionally pinned by finite
-differences in tests/test_bpla_grad.py).
+reference's tools cannot be built here and it ships no fixtures, so these pin
+the oracle and the GPU engine against regressions (the oracle is pinned to the
+reference's own DP code in tests/test_oracle_dp_pinning.py; the gradients are
+additionally pinned by finite differences in tests/test_bpla_grad.py).
 
 Run:  python tests/golden/make_golden_ext.py
 """

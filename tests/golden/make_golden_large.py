@@ -21,8 +21,9 @@ CONFIGS, seed 0x5EED0000 + config id), stored verbatim; base-pairing
 probabilities are the engine's synthetic fold (stem_kernel_amd.fold, host
 C++), whose bytes are pinned by a SHA-256 stored beside the values.
 Expected values come from the CPU oracle (oracle/sk_oracle.c), a line-by-line
-restatement of the reference (parity against the reference's own output is
-unpinned: it ships no fixtures and its DP does not build here).
+restatement of the reference (pinned to the reference's own DP code on small
+inputs, tests/test_oracle_dp_pinning.py; the reference ships no fixtures,
+DESIGN.md §7).
 
 Run:  python tests/golden/make_golden_large.py [--dag-only]     (~1-2 min on 8 cores)
 """

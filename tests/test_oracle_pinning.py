@@ -4,7 +4,7 @@ oracle/_ref/libskref.so is the reference's own common/rna.cpp,
 common/profile.cpp and stem_kernel_lite/ribosum.cpp, compiled unmodified from
 /root/reference by oracle/Makefile (the only hot-path translation units that
 build with nothing but the C++ standard library).  The DP kernels themselves
-cannot be built here (Boost, ViennaRNA, config.h): see DESIGN.md §Oracle.
+are pinned in tests/test_oracle_dp_pinning.py: see DESIGN.md §7.
 """
 import ctypes as C
 
