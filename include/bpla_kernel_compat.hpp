@@ -20,6 +20,13 @@
 //     operator()(x, y)                               bpla_kernel.h:13-45
 //     static compute_gradients(x, y, score_table, param, d)
 //                                                    bpla_kernel.cpp:385-401
+//   AAProfileSequence (N_AA, char2aa, size, operator[], n_seqs)
+//                                                    common/aaprofile.h:9-77
+//   AAMData = Data<AAProfileSequence, list<string>>, DataLoader<AAMData>,
+//   DataLoaderFactory<DataLoader<AAMData> >          data.h:52, 118-209
+//   BPLAKernel<double,AAMData>(score_table [23][23], noBP = true, ...)
+//     the la_kernel tool: the body of la_main.cpp:118-135 compiles with the
+//     include swapped and runs on csrc/kernels/la_protein.hip
 //   BPMatrix::Options                                common/bpmatrix.h:17-38
 //   KernelMatrix<V>                                  common/kernel_matrix.h:13-108
 //
@@ -60,8 +67,72 @@ struct Data : RowsData {
 
 typedef Data<ProfileSequence, std::list<std::string>> MData;
 
+// AAProfileSequence (common/aaprofile.h:9-77, aaprofile.cpp:13-60): the
+// integer count of every amino-acid letter per alignment column, everything
+// else in slot N_AA.  Host-side view for callers; the engine builds its own
+// from the rows (sk_dataset_add_protein).
+class AAProfileSequence {
+ public:
+  typedef float value_type;
+  typedef std::vector<value_type> Column;
+  typedef std::vector<Column>::const_iterator const_iterator;
+  static const unsigned int N_AA = 23;
+  static int char2aa(int c) { return sk_char2aa(c); }
+
+  AAProfileSequence() : n_seqs_(0) {}
+  template <class T>
+  AAProfileSequence(const T& ma) : n_seqs_(0) {
+    profile_.assign(ma.begin()->size(), Column(N_AA + 1, 0.0f));
+    for (typename T::const_iterator x = ma.begin(); x != ma.end(); ++x) add_sequence(*x);
+  }
+  value_type n_seqs() const { return n_seqs_; }
+  unsigned int size() const { return (unsigned int)profile_.size(); }
+  const Column& operator[](unsigned int i) const { return profile_[i]; }
+  const_iterator begin() const { return profile_.begin(); }
+  const_iterator end() const { return profile_.end(); }
+  void add_sequence(const std::string& seq, value_type w = 1.0f) {
+    if (profile_.size() != seq.size()) throw "alignment error";
+    for (size_t i = 0; i != profile_.size(); ++i) profile_[i][char2aa((unsigned char)seq[i])] += w;
+    n_seqs_ += w;
+  }
+
+ private:
+  value_type n_seqs_;
+  std::vector<Column> profile_;
+};
+
+// AAMData (bpla_kernel/data.h:52): a protein alignment; Data(ma) only, it
+// has no base-pairing weights (data.cpp:51-63).
+template <>
+struct Data<AAProfileSequence, std::list<std::string>> : RowsData {
+  typedef AAProfileSequence Seq;
+  Data() {}
+  explicit Data(const std::list<std::string>& ma) : seq(ma) { rows.assign(ma.begin(), ma.end()); }
+  uint size() const { return seq.size(); }
+  AAProfileSequence seq;
+};
+typedef Data<AAProfileSequence, std::list<std::string>> AAMData;
+
 template <class D>
 class DataLoader;
+
+// DataLoader<AAMData> (data.h:118-128, data.cpp:235-293)
+template <>
+class DataLoader<AAMData> {
+ public:
+  typedef AAMData Data;
+  explicit DataLoader(const char* filename) : file_(filename) {}
+  Data* get() {
+    std::list<std::string> ma;
+    if (!file_.next(ma)) return nullptr;
+    for (const std::string& r : ma)
+      if (r.size() != ma.front().size()) throw "wrong alignment";  // data.cpp:284-288
+    return new AAMData(ma);
+  }
+
+ private:
+  SeqFile file_;
+};
 
 template <>
 class DataLoader<MData> {
@@ -98,6 +169,16 @@ class DataLoaderFactory {
  private:
   BPMatrix::Options bp_opts_;
   bool use_bp_;
+};
+
+// DataLoaderFactory<DataLoader<AAMData> > (data.h:193-209)
+template <>
+class DataLoaderFactory<DataLoader<AAMData>> {
+ public:
+  typedef DataLoader<AAMData> Loader;
+  typedef Loader::Data Data;
+  DataLoaderFactory() {}
+  Loader* get_loader(const char* filename, const char* /*pf_scales*/ = nullptr) const { return new Loader(filename); }
 };
 
 template <class ValueType, class DataT>
@@ -145,7 +226,41 @@ class BPLAKernel : public KernelBase<ValueType, DataT> {
   }
 };
 
+// BPLAKernel<V, AAMData> (bpla_kernel.cpp:406; la_main.cpp:133): LAScore over
+// a [23][23] table in char2aa order.  noBP must be true: AAMData(ma) carries
+// no base-pairing weights for BPLAScore to read.
+template <class ValueType>
+class BPLAKernel<ValueType, AAMData> : public KernelBase<ValueType, AAMData> {
+ public:
+  typedef ValueType value_type;
+  typedef AAMData Data;
+  template <class Table>
+  BPLAKernel(const Table& score_table, bool noBP, bool SW = false, value_type gap = 1, value_type ext = 1,
+             value_type /*alpha*/ = 1, value_type beta = 1)
+      : KernelBase<ValueType, AAMData>(SW ? SK_AA_LA_SW : SK_AA_LA) {
+    if (!noBP) throw "BPLAKernel<AAMData>: noBP must be true (protein examples have no base-pairing weights)";
+    for (int a = 0; a < 23; ++a)
+      for (int b = 0; b < 23; ++b) this->p_.aa_score_table[23 * a + b] = score_table[a][b];
+    this->p_.gap = gap;
+    this->p_.ext = ext;
+    this->p_.beta = beta;
+  }
+};
+
 }  // namespace bpla
+
+template <>
+struct ExampleTraits<bpla::AAMData> {
+  static void add(sk_dataset* ds, const std::string& label, const bpla::AAMData& d, const BuildSpec&) {
+    std::vector<const char*> r;
+    for (const auto& s : d.rows) r.push_back(s.c_str());
+    check(sk_dataset_add_protein(ds, label.c_str(), (int)r.size(), r.data()));
+  }
+  static void mix(Fnv& f, const bpla::AAMData& d) {
+    mix_rows(f, d);
+    f("aa", 2);  // never the cached dataset of the same rows read as RNA
+  }
+};
 
 template <class S, class IS>
 struct ExampleTraits<bpla::Data<S, IS>> {
@@ -164,6 +279,8 @@ using skc::bpla::BPMatrix;
 using skc::bpla::Data;
 using skc::bpla::DataLoader;
 using skc::bpla::DataLoaderFactory;
+using skc::bpla::AAMData;
+using skc::bpla::AAProfileSequence;
 using skc::bpla::MData;
 using skc::bpla::ProfileSequence;
 typedef unsigned int uint;

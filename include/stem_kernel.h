@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define SK_ABI_VERSION 2
+#define SK_ABI_VERSION 3
 
 typedef enum {
   SK_OK = 0,
@@ -60,7 +60,12 @@ typedef enum {
   SK_LA_SW = 12,       /* local_alignment_max with LAScore               --noBP --SW */
   /* StemKernel<double,BPMat>::full_dp of stem_kernel/ (stem_kernel.cpp:282-351)
    * over single sequences (row 0, lowercased as the loader does) */
-  SK_STEM4D = 13
+  SK_STEM4D = 13,
+  /* BPLAKernel<double,AAMData> of bpla_kernel/ (la_kernel: la_main.cpp:131-135,
+   * instantiated at bpla_kernel.cpp:406) over protein datasets
+   * (sk_dataset_add_protein): LAScore over the 23 amino-acid letters, noBP */
+  SK_AA_LA = 14,       /* local_alignment_exp                                        */
+  SK_AA_LA_SW = 15     /* local_alignment_max                            --SW        */
 } sk_kernel_kind;
 
 /* Kernel parameters; defaults are stem_kernel_lite/main.cpp:103-149
@@ -98,6 +103,12 @@ typedef struct {
    * posteriors are NaN and no position is anchored); 1: the intended -inf
    * test (anchored constraints). */
   int32_t ali_zerop_fixed;
+  /* SK_AA_LA / SK_AA_LA_SW: the 23x23 amino-acid score table, [x residue][y
+   * residue] in char2aa order ARNDCQEGHILKMFPSTWYVBZX (common/aaprofile.cpp:
+   * 13-23); default BLOSUM62 (la_main.cpp:21-46).  These kinds use gap, ext
+   * and beta (float-rounded defaults -10, -1, 0.11, la_main.cpp:87-90); no
+   * other kind reads the field. */
+  double aa_score_table[529];
 } sk_kernel_params;
 
 void sk_kernel_params_default(sk_kernel_params *p, int32_t kind);
@@ -144,6 +155,23 @@ int sk_dataset_add_synthetic(sk_dataset *ds, int32_t n, const char *const *seqs,
 int sk_dataset_add_synthetic_rows(sk_dataset *ds, int32_t n, int32_t n_rows,
                                   const char *const *rows, const char *const *labels,
                                   float th, int32_t n_threads);
+/* Append one protein example = one alignment of n_rows rows of equal length
+ * over the amino-acid alphabet (unequal rows: SK_ERR_INVALID, "wrong
+ * alignment", bpla_kernel/data.cpp:284-288; 4,096 rows or more:
+ * SK_ERR_UNSUPPORTED).  Each column holds the integer count of every letter
+ * of char2aa, any other character ('-', '*', 'U', ...) counted in slot 23
+ * (AAProfileSequence::add_sequence, common/aaprofile.cpp:49-60).  A dataset is
+ * RNA or protein, decided by its first example: mixing gives SK_ERR_INVALID,
+ * and so does an SK_AA_* kind on an RNA dataset or any other kind on a
+ * protein dataset.  Replaces: new AAMData(ma)  bpla_kernel/data.cpp:263-293. */
+int sk_dataset_add_protein(sk_dataset *ds, const char *label, int n_rows,
+                           const char *const *rows);
+/* AAProfileSequence of protein example i: prof24 gets len*24 floats (the 23
+ * letters of char2aa, then "other"), *n_seqs the row count. */
+int sk_dataset_aa_profile(const sk_dataset *ds, int i, float *prof24, float *n_seqs);
+/* char2aa (common/aaprofile.cpp:13-23): 0..22 for ARNDCQEGHILKMFPSTWYVBZX in
+ * either case, 23 for everything else. */
+int sk_char2aa(int c);
 /* Append a copy of example i of src (its built DAG, profile and weights: no
  * rebuild) to dst, e.g. to assemble the pair a per-pair Kernel::operator()
  * call evaluates from examples built once.  dst must not be uploaded yet. */
@@ -498,6 +526,10 @@ int sk_sync_timing(sk_context *ctx);
  * lane), shifted by 4 for the banded (partial_dp) variant and by 8 for the
  * column-pipelined full_dp kernel. */
 int sk_last_classes(const sk_context *ctx, uint32_t *stem_maxk_mask, uint32_t *stem4d_mask);
+/* Protein local-alignment kernels the last compute call launched
+ * (csrc/kernels/la_protein.hip): bit 0 the code kernel (pairs of examples
+ * whose every column holds one residue kind), bit 1 the profile kernel. */
+int sk_last_la_protein(const sk_context *ctx, uint32_t *mask);
 /* The number of DAG stem class launches of the last compute call that read one
  * Gamma table per y example, built by a table kernel ahead of the launch and
  * shared by every workgroup on that y (0 for a null context).  The other

@@ -25,7 +25,9 @@ STATUS = {
 # sk_kernel_kind
 FMT_FASTA, FMT_CLUSTAL, FMT_MAF = range(3)
 (SU_STEM, SI_STEM, SU_STR, SI_STR, SU_STEM_STR, SI_STEM_STR, LSU_STEM, LSU_STEM_STR, NAIVE_STR,
- BPLA, LA, BPLA_SW, LA_SW, STEM4D) = range(14)
+ BPLA, LA, BPLA_SW, LA_SW, STEM4D, AA_LA, AA_LA_SW) = range(16)
+# amino-acid letters in char2aa order (common/aaprofile.cpp:13-23); index 23 = everything else
+AA_LETTERS = "ARNDCQEGHILKMFPSTWYVBZX"
 
 
 class KernelParams(C.Structure):
@@ -36,6 +38,7 @@ class KernelParams(C.Structure):
         ("mismatch", C.c_double), ("ext", C.c_double), ("score_table", C.c_double * 16),
         ("subst", C.c_double), ("bp_bound", C.c_double), ("bp_model", C.c_int32),
         ("loop", C.c_uint32), ("ali_bound", C.c_double), ("ali_zerop_fixed", C.c_int32),
+        ("aa_score_table", C.c_double * 529),
     ]
 
 
@@ -60,6 +63,10 @@ SIGNATURES = {
                                            C.POINTER(C.c_char_p), C.c_float, C.c_int32]),
     "sk_dataset_add_synthetic_rows": (C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(C.c_char_p),
                                                 C.POINTER(C.c_char_p), C.c_float, C.c_int32]),
+    "sk_dataset_add_protein": (C.c_int, [_P, C.c_char_p, C.c_int, C.POINTER(C.c_char_p)]),
+    "sk_dataset_aa_profile": (C.c_int, [_P, C.c_int, _F32P, _F32P]),
+    "sk_char2aa": (C.c_int, [C.c_int]),
+    "sk_last_la_protein": (C.c_int, [_P, C.POINTER(C.c_uint32)]),
     "sk_dataset_size": (C.c_int, [_P]),
     "sk_dataset_add_copy": (C.c_int, [_P, _P, C.c_int32]),
     "sk_dataset_export": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t,
@@ -185,9 +192,10 @@ def default_params(kind=SU_STEM_STR, **over):
     p = KernelParams()
     lib().sk_kernel_params_default(C.byref(p), kind)
     for k, v in over.items():
-        if k == "score_table":
+        if k in ("score_table", "aa_score_table"):
+            arr = getattr(p, k)
             for i, t in enumerate(v):
-                p.score_table[i] = float(t)
+                arr[i] = float(t)
         else:
             setattr(p, k, v)
     return p

@@ -47,6 +47,11 @@ struct Example {
   std::vector<float> bpf_p;
   std::vector<uint32_t> roots;
   std::vector<uint32_t> max_pa;
+  // protein example (AAMData(ma), bpla_kernel/data.cpp:263-293): the
+  // AAProfileSequence counts [len][24] (common/aaprofile.cpp:49-60); none of
+  // the RNA fields above but len, n_rows, rows and n_seqs is filled
+  bool protein = false;
+  std::vector<float> aa_prof;
   int n_nodes() const { return (int)first.size(); }
   int n_edges() const { return (int)edge_to.size(); }
 };

@@ -446,4 +446,51 @@ hipError_t launch_bpla_fast(const BplaLaunch& P, int grid, int nwaves, hipStream
 hipError_t launch_combine(const double* stem, const double* str, double* out, int64_t n,
                           int32_t mode, double alpha, double beta, hipStream_t st);
 
+// Protein local-alignment kernels (la_protein.hip; BPLAKernel<double,AAMData>,
+// bpla_kernel.cpp:64-157 with LAScore over the 23 amino-acid letters).
+constexpr int kAaSlots = 24;  // N_AA + 1: the letters of char2aa, then "other"
+// device image of a protein dataset: per position its 24 integer counts
+// (float) and, where one slot holds the whole column, that slot's index
+struct LaProtSet {
+  const int32_t* ex_len = nullptr;
+  const int32_t* ex_pos_base = nullptr;
+  const float* prof = nullptr;    // [positions][24]
+  const uint8_t* code = nullptr;  // [positions], 0..23 (coded examples only)
+};
+struct LaProtLaunch {
+  LaProtSet xset, yset;
+  const double* table = nullptr;  // 529: [x residue][y residue]
+  double beta = 0.0, gap = 0.0, ext = 0.0;
+  double beta_gap = 0.0, beta_ext = 0.0;  // exp(beta*gap), exp(beta*ext)
+  int32_t sw = 0;
+  const int32_t* xs = nullptr;
+  const int32_t* ys = nullptr;
+  const int64_t* oidx = nullptr;  // out[oidx[k]] = K(pair k) (nullptr: out[k])
+  int64_t n_pairs = 0;
+  double* out = nullptr;
+  unsigned long long* pair_counter = nullptr;
+  int32_t lds_max_len = 0;  // even, >= 64 (streamed strips)
+};
+// workgroup LDS of the code kernel: the 24x24 factor table, then per wave the
+// boundary row {M, X, Y} [maxlen + 2] and the y codes [maxlen]
+__host__ __device__ inline size_t la_prot_code_wave_lds_bytes(int maxlen) {
+  const size_t b = (size_t)3 * (maxlen + 2) * 8 + (size_t)maxlen;
+  return (b + 15) & ~(size_t)15;
+}
+__host__ __device__ inline size_t la_prot_code_lds_bytes(int maxlen, int nwaves) {
+  return (size_t)kAaSlots * kAaSlots * 8 + (size_t)nwaves * la_prot_code_wave_lds_bytes(maxlen);
+}
+// workgroup LDS of the profile kernel: the 23x23 table (padded to 24x24), then
+// per wave the boundary row {M, X, Y} [maxlen + 2] and the y columns
+// [maxlen][24] float (slot 23: the column's sum over the 23 letters)
+__host__ __device__ inline size_t la_prot_prof_wave_lds_bytes(int maxlen) {
+  const size_t b = (size_t)3 * (maxlen + 2) * 8 + (size_t)maxlen * kAaSlots * 4;
+  return (b + 15) & ~(size_t)15;
+}
+__host__ __device__ inline size_t la_prot_prof_lds_bytes(int maxlen, int nwaves) {
+  return (size_t)kAaSlots * kAaSlots * 8 + (size_t)nwaves * la_prot_prof_wave_lds_bytes(maxlen);
+}
+hipError_t launch_la_prot_code(const LaProtLaunch& P, int grid, int nwaves, hipStream_t st);
+hipError_t launch_la_prot_prof(const LaProtLaunch& P, int grid, int nwaves, hipStream_t st);
+
 }  // namespace sk

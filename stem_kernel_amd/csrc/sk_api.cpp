@@ -22,6 +22,7 @@
 #include <thread>
 #include <type_traits>
 #include <atomic>
+#include <cctype>
 #include <string>
 #include <system_error>
 #include <vector>
@@ -34,6 +35,7 @@
 #include "kernels/device_set.h"
 #include "kernels/launch.h"
 #include "ribosum85_60.inc"
+#include "blosum62.inc"
 
 using sk::DevSet;
 using sk::Example;
@@ -235,6 +237,15 @@ struct sk_dataset {
   DevSet dev;
   DeviceBuffers buf;
   HostPack pack;
+  // protein examples (sk_dataset_add_protein): their own packed image, the
+  // arrays of sk::LaProtSet and per example whether every column holds one
+  // residue kind (the code kernel's pairs); the RNA image above stays empty
+  struct ProtPack {
+    std::vector<int32_t> ex_len, ex_pos_base;
+    std::vector<uint8_t> ex_coded, code;
+    std::vector<float> prof;
+  } ppack;
+  sk::LaProtSet pdev;
   std::string err;
   // x-role leaf-column closed forms (sk_prep_kernel) for one loop_gap: they
   // depend only on the dataset (immutable once uploaded) and loop_gap
@@ -245,6 +256,58 @@ struct sk_dataset {
   std::vector<std::shared_ptr<Stem4dTables>> s4;
 };
 constexpr size_t kS4Sets = 4;
+
+// A dataset is RNA or protein, decided by its first example.
+static bool ds_protein(const sk_dataset* ds) { return !ds->ex.empty() && ds->ex[0].protein; }
+// appending an example of the other sort: refused (the message in ds->err)
+static bool ds_mixes(sk_dataset* ds, bool protein) {
+  if (ds->ex.empty() || ds->ex[0].protein == protein) return false;
+  ds->err = protein ? "protein example added to an RNA dataset" : "RNA example added to a protein dataset";
+  return true;
+}
+// examples of this many rows or more are refused: below it every float
+// product and sum of LAScore's weight n is an exact integer (< 2^24)
+constexpr int kAaMaxRows = 4096;
+
+// char2aa (common/aaprofile.cpp:13-23)
+static int char2aa(int c) {
+  if (c < 0 || c > 255) return 23;
+  const int u = std::toupper(c);
+  for (int k = 0; k < 23; ++k)
+    if (SK_AA_LETTERS[k] == u) return k;
+  return 23;
+}
+
+// Packed image of a protein dataset (sk::LaProtSet): per position the 24
+// counts and, in examples whose every column has one non-empty slot, that
+// slot (23 elsewhere; the code kernel takes only pairs of such examples).
+static void pack_protein(sk_dataset* ds) {
+  sk_dataset::ProtPack& P = ds->ppack;
+  P = sk_dataset::ProtPack();
+  size_t pos = 0;
+  for (const Example& X : ds->ex) pos += (size_t)X.len;
+  P.prof.reserve(pos * sk::kAaSlots);
+  P.code.reserve(pos);
+  for (const Example& X : ds->ex) {
+    P.ex_len.push_back(X.len);
+    P.ex_pos_base.push_back((int32_t)P.code.size());
+    bool coded = true;
+    for (int i = 0; i < X.len; ++i) {
+      const float* c = X.aa_prof.data() + (size_t)i * sk::kAaSlots;
+      int used = 0, slot = sk::kAaSlots - 1;
+      for (int k = 0; k < sk::kAaSlots; ++k)
+        if (c[k] != 0.0f) {
+          ++used;
+          slot = k;
+        }
+      coded = coded && used == 1;
+      P.code.push_back((uint8_t)slot);
+    }
+    if (!coded) std::fill(P.code.end() - X.len, P.code.end(), (uint8_t)(sk::kAaSlots - 1));
+    P.ex_coded.push_back(coded ? 1 : 0);
+    P.prof.insert(P.prof.end(), X.aa_prof.begin(), X.aa_prof.end());
+  }
+}
 
 struct Stem4dBatch {
   sk::Stem4dPair* pairs = nullptr;
@@ -325,6 +388,7 @@ struct sk_context {
   // per 4-D stem class
   uint32_t last_stem_classes = 0, last_s4d_classes = 0;
   int32_t last_gamma_shared = 0;  // class launches of the last call that read shared Gamma tables
+  uint32_t last_la_protein = 0;   // protein LA kernels of the last call: 1 code, 2 profile
   // RCCL communicator of sk_comm_init (ncclComm_t, csrc/host/shard.cpp)
   void* comm = nullptr;
 };
@@ -1576,9 +1640,10 @@ int pack_dataset(sk_dataset* ds, std::string& err, const std::function<void()>* 
 
 // ------------------------------------------------------------ parameters
 bool kind_is_bpla(int k) { return k >= SK_BPLA && k <= SK_LA_SW; }
+bool kind_is_aa(int k) { return k == SK_AA_LA || k == SK_AA_LA_SW; }
 bool kind_has_stem(int k) {
   return k != SK_SU_STR && k != SK_SI_STR && k != SK_NAIVE_STR && !kind_is_bpla(k) &&
-         k != SK_STEM4D;
+         k != SK_STEM4D && !kind_is_aa(k);
 }
 bool kind_has_str(int k) {
   return k == SK_SU_STR || k == SK_SI_STR || k == SK_SU_STEM_STR || k == SK_SI_STEM_STR ||
@@ -1913,6 +1978,153 @@ int run_bpla(sk_context* ctx, sk_dataset* xs_, sk_dataset* ys_, const sk_kernel_
   if (host_stats)
     fprintf(stderr, "[sk bpla host] plan %.3f ms, uploads %.3f ms, launches %.3f ms, wait %.3f ms (GPU %.3f ms)\n",
             tb1 - tb0, tb2 - tb1, tb3 - tb2, now_ms() - tb3, ctx->async ? -1.0 : ctx->last_stem_ms);
+  return SK_OK;
+}
+
+// Protein local-alignment kinds (la_protein.hip): pairs of two coded examples
+// (every column one residue kind) go to the code kernel, the rest to the
+// profile kernel; one launch each, results straight to out_dev.
+int run_la_protein(sk_context* ctx, sk_dataset* xs_, sk_dataset* ys_, const sk_kernel_params* kp,
+                   const int32_t* x, const int32_t* y, int64_t n, double* out_dev) {
+  const bool sw = kp->kind == SK_AA_LA_SW;
+  static const bool host_stats = std::getenv("SK_HOST_STATS") != nullptr;
+  const sk_dataset::ProtPack& PX = xs_->ppack;
+  const sk_dataset::ProtPack& PY = ys_->ppack;
+  // one pass: cells, the code pairs first (the permutation undone through
+  // oidx), the longest y of each sort (the kernels' LDS)
+  std::vector<uint8_t> codek((size_t)n);
+  double cells = 0.0;
+  int64_t n_code = 0;
+  int32_t ymax_code = 0, ymax_prof = 0;
+  for (int64_t k = 0; k < n; ++k) {
+    const int32_t a = x[k], b = y[k];
+    cells += (double)PX.ex_len[a] * (double)PY.ex_len[b];
+    const uint8_t c = PX.ex_coded[a] & PY.ex_coded[b];
+    codek[(size_t)k] = c;
+    n_code += c;
+    int32_t& m = c ? ymax_code : ymax_prof;
+    m = std::max(m, PY.ex_len[b]);
+  }
+  ctx->last_cells = cells;
+  // waves per workgroup: halved until the LDS fits, as run_bpla does
+  const int len_code = (std::max(ymax_code, 64) + 1) & ~1, len_prof = (std::max(ymax_prof, 64) + 1) & ~1;
+  int w_code = 4, w_prof = 4;
+  while (w_code > 1 && sk::la_prot_code_lds_bytes(len_code, w_code) > 163840) w_code /= 2;
+  while (w_prof > 1 && sk::la_prot_prof_lds_bytes(len_prof, w_prof) > 163840) w_prof /= 2;
+  if (n_code && sk::la_prot_code_lds_bytes(len_code, w_code) > 163840)
+    return fail(ctx, SK_ERR_UNSUPPORTED, "sequence too long for the protein LA kernel LDS (6,366 residues)");
+  if (n_code < n && sk::la_prot_prof_lds_bytes(len_prof, w_prof) > 163840)
+    return fail(ctx, SK_ERR_UNSUPPORTED, "alignment too long for the protein LA profile kernel LDS (1,326 columns)");
+  std::vector<int32_t> px, py;
+  std::vector<int64_t> oidx;
+  const bool permute = n_code != 0 && n_code != n;
+  if (permute) {
+    px.resize((size_t)n);
+    py.resize((size_t)n);
+    oidx.resize((size_t)n);
+    int64_t f = 0, g = n_code;
+    for (int64_t k = 0; k < n; ++k) {
+      const int64_t d = codek[(size_t)k] ? f++ : g++;
+      px[(size_t)d] = x[k];
+      py[(size_t)d] = y[k];
+      oidx[(size_t)d] = k;
+    }
+    x = px.data();
+    y = py.data();
+  }
+  const size_t nb = (size_t)n;
+  int rc = ensure_work(ctx, 529 * 8 + 64 + nb * 8 + (permute ? nb * 8 : 0) + 8192);
+  if (rc) return rc;
+  // the call's inputs and zeroed counters go up in one copy (run_bpla)
+  double* d_tb;
+  unsigned long long* d_ctr;
+  int32_t *d_px, *d_py;
+  int64_t* d_oidx;
+  auto lay = [&](Arena& U) {
+    d_tb = U.take<double>(529);
+    d_ctr = U.take<unsigned long long>(8);
+    d_px = U.take<int32_t>(nb);
+    d_py = U.take<int32_t>(nb);
+    d_oidx = permute ? U.take<int64_t>(nb) : nullptr;
+  };
+  Arena A{static_cast<char*>(ctx->work), 0, ctx->work_bytes};
+  Arena U{nullptr, 0, 0};
+  lay(U);  // (sizes only)
+  const size_t up_bytes = U.off;
+  if (ctx->async) {
+    char* ub = nullptr;
+    SK_HIP(ctx, sk::up_reserve(ctx, up_bytes, &ub));
+    U = Arena{ub, 0, up_bytes};
+    lay(U);
+  } else {
+    lay(A);
+    U.base = A.base;
+  }
+  hipStream_t S = ctx->stream;
+  {
+    thread_local std::vector<char> hb;
+    hb.assign(up_bytes, 0);
+    auto put = [&](const void* dptr, const void* src, size_t bytes) {
+      if (bytes) std::memcpy(hb.data() + (static_cast<const char*>(dptr) - U.base), src, bytes);
+    };
+    put(d_tb, kp->aa_score_table, 529 * 8);
+    put(d_px, x, nb * 4);
+    put(d_py, y, nb * 4);
+    if (permute) put(d_oidx, oidx.data(), nb * 8);
+    if (ctx->async)
+      SK_HIP(ctx, sk::up_copy(ctx, hb.data(), up_bytes, S));
+    else
+      SK_HIP(ctx, sk::h2d(ctx, U.base, hb.data(), up_bytes, S));
+  }
+  sk::LaProtLaunch T;
+  T.xset = xs_->pdev;
+  T.yset = ys_->pdev;
+  T.table = d_tb;
+  T.beta = kp->beta;
+  T.gap = kp->gap;
+  T.ext = kp->ext;
+  T.beta_gap = std::exp(kp->beta * kp->gap);  // bpla_kernel.cpp:71-72
+  T.beta_ext = std::exp(kp->beta * kp->ext);
+  T.sw = sw ? 1 : 0;
+  T.out = out_dev;
+  SK_HIP(ctx, hipEventRecord(ctx->ev0, S));
+  if (n_code) {
+    sk::LaProtLaunch C = T;
+    C.xs = d_px;
+    C.ys = d_py;
+    C.oidx = d_oidx;
+    C.n_pairs = n_code;
+    C.pair_counter = d_ctr;
+    C.lds_max_len = len_code;
+    const size_t lds = sk::la_prot_code_lds_bytes(len_code, w_code);
+    const int per_cu = std::max(1, std::min<int>((int)(163840 / lds), 16 / w_code));
+    const int64_t g = std::min<int64_t>((int64_t)ctx->n_cu * per_cu, (n_code + w_code - 1) / w_code);
+    SK_HIP(ctx, sk::lev_mark(ctx, S));
+    SK_HIP(ctx, sk::launch_la_prot_code(C, (int)g, w_code, S));
+    SK_HIP(ctx, sk::lev_mark(ctx, S));
+  }
+  if (n_code < n) {
+    sk::LaProtLaunch G = T;
+    G.xs = d_px + n_code;
+    G.ys = d_py + n_code;
+    G.oidx = d_oidx ? d_oidx + n_code : nullptr;
+    G.n_pairs = n - n_code;
+    G.pair_counter = d_ctr + 1;
+    G.lds_max_len = len_prof;
+    const size_t lds = sk::la_prot_prof_lds_bytes(len_prof, w_prof);
+    const int per_cu = std::max(1, std::min<int>((int)(163840 / lds), 8 / w_prof));
+    const int64_t g = std::min<int64_t>((int64_t)ctx->n_cu * per_cu, (G.n_pairs + w_prof - 1) / w_prof);
+    SK_HIP(ctx, sk::lev_mark(ctx, S));
+    SK_HIP(ctx, sk::launch_la_prot_prof(G, (int)g, w_prof, S));
+    SK_HIP(ctx, sk::lev_mark(ctx, S));
+  }
+  SK_HIP(ctx, hipEventRecord(ctx->ev1, S));
+  ctx->last_launches = (n_code ? 1 : 0) + (n_code < n ? 1 : 0);
+  ctx->last_la_protein = (n_code ? 1u : 0u) | (n_code < n ? 2u : 0u);
+  SK_HIP(ctx, sk::call_finish(ctx, S, true, false));
+  if (host_stats)
+    fprintf(stderr, "[sk la protein] code kernel %lld pairs (%d waves), profile kernel %lld pairs (%d waves)\n",
+            (long long)n_code, w_code, (long long)(n - n_code), w_prof);
   return SK_OK;
 }
 
@@ -2350,13 +2562,21 @@ int run_pairs(sk_context* ctx, sk_dataset* xs_, sk_dataset* ys_, const sk_kernel
   rc = check_set(ctx, ys_);
   if (rc) return rc;
   if (n < 0) return fail(ctx, SK_ERR_INVALID, "negative pair count");
-  if (kp->kind < SK_SU_STEM || kp->kind > SK_STEM4D)
+  if (kp->kind < SK_SU_STEM || kp->kind > SK_AA_LA_SW)
     return fail(ctx, SK_ERR_UNSUPPORTED, "unknown kernel kind");
+  // no silent reinterpretation of one alphabet as the other
+  if (ds_protein(xs_) != ds_protein(ys_) && !xs_->ex.empty() && !ys_->ex.empty())
+    return fail(ctx, SK_ERR_INVALID, "a protein dataset paired with an RNA dataset");
+  if (kind_is_aa(kp->kind) && !(ds_protein(xs_) && ds_protein(ys_)) && n > 0)
+    return fail(ctx, SK_ERR_INVALID, "an amino-acid kernel kind (SK_AA_LA*) needs protein datasets, these hold RNA examples");
+  if (!kind_is_aa(kp->kind) && (ds_protein(xs_) || ds_protein(ys_)))
+    return fail(ctx, SK_ERR_INVALID, "an RNA kernel kind on a protein dataset (use SK_AA_LA or SK_AA_LA_SW)");
   ctx->last_stem_ms = ctx->last_str_ms = ctx->last_cells = 0.0;
   ctx->last_launches = 0;
   sk::lev_reset(ctx);
   ctx->last_stem_classes = ctx->last_s4d_classes = 0;
   ctx->last_gamma_shared = 0;
+  ctx->last_la_protein = 0;
   if (n == 0) return SK_OK;
   const int nx = (int)xs_->ex.size(), ny = (int)ys_->ex.size();
   for (int64_t k = 0; k < n; ++k)
@@ -2364,6 +2584,7 @@ int run_pairs(sk_context* ctx, sk_dataset* xs_, sk_dataset* ys_, const sk_kernel
       return fail(ctx, SK_ERR_RANGE, "pair index out of range");
   SK_HIP(ctx, sk::call_begin(ctx));
   if (kind_is_bpla(kp->kind)) return run_bpla(ctx, xs_, ys_, kp, x, y, n, out_dev);
+  if (kind_is_aa(kp->kind)) return run_la_protein(ctx, xs_, ys_, kp, x, y, n, out_dev);
   if (kp->kind == SK_STEM4D) {
     // synchronous batches (each waits for its spans): its totals are final
     rc = run_stem4d(ctx, xs_, ys_, kp, x, y, n, out_dev);
@@ -3077,6 +3298,8 @@ int bpla_gradients(sk_context* ctx, sk_dataset* xs_, sk_dataset* ys_, const sk_k
   if (rc) return rc;
   rc = check_set(ctx, ys_);
   if (rc) return rc;
+  if (ds_protein(xs_) || ds_protein(ys_))
+    return fail(ctx, SK_ERR_INVALID, "BPLA gradients on a protein dataset");
   if (n <= 0) return n < 0 ? fail(ctx, SK_ERR_INVALID, "negative pair count") : SK_OK;
   SK_HIP(ctx, sk::call_begin(ctx));  // (synchronous: a fresh timing set, not a pending one)
   for (int64_t k = 0; k < n; ++k) {
@@ -3393,6 +3616,13 @@ void example_fields(IO& io, E& X) {
   io.vec(X.roots);
   io.vec(X.max_pa);
 }
+template <class IO, class E>
+void protein_fields(IO& io, E& X) {
+  uint8_t pb = X.protein ? 1 : 0;
+  io.pod(pb);
+  if constexpr (std::is_same_v<IO, ExReader>) X.protein = pb != 0;
+  io.vec(X.aa_prof);
+}
 constexpr uint32_t kExMagic = 0x58454b53u;  // "SKEX"
 
 // The invariants example_build.cpp establishes and the packer and kernels
@@ -3403,6 +3633,24 @@ bool example_valid(const Example& X) {
   if (X.len < 0 || X.n_rows < 1 || X.rows.size() != (size_t)X.n_rows) return false;
   for (const auto& r : X.rows)
     if (r.size() != L) return false;
+  if (X.protein) {
+    // integer counts, every column summing to the row count (< 4,096 rows),
+    // and none of the RNA fields
+    if (X.n_rows >= kAaMaxRows || X.n_seqs != (float)X.n_rows || X.aa_prof.size() != L * sk::kAaSlots) return false;
+    for (size_t i = 0; i < L; ++i) {
+      float sum = 0.0f;
+      for (int k = 0; k < sk::kAaSlots; ++k) {
+        const float c = X.aa_prof[i * sk::kAaSlots + k];
+        if (!(c >= 0.0f) || c != std::floor(c)) return false;
+        sum += c;
+      }
+      if (sum != (float)X.n_rows) return false;
+    }
+    return !X.has_bp && X.prof5.empty() && X.pos_weight.empty() && X.bpp.empty() && X.first.empty() &&
+           X.last.empty() && X.weight.empty() && X.edge_off.empty() && X.edge_to.empty() && X.edge_gaps.empty() &&
+           X.bpf_off.empty() && X.bpf_code.empty() && X.bpf_p.empty() && X.roots.empty() && X.max_pa.empty();
+  }
+  if (!X.aa_prof.empty()) return false;
   if (X.prof5.size() != L * 5) return false;
   const size_t nn = X.first.size();
   if (X.last.size() != nn || X.weight.size() != nn) return false;
@@ -3467,6 +3715,13 @@ void sk_kernel_params_default(sk_kernel_params* p, int32_t kind) {
   if (kind >= SK_BPLA && kind <= SK_LA_SW) {
     p->gap = (double)-8.0f;
     p->alpha = (double)4.5f;
+    p->beta = (double)0.11f;
+  }
+  // la_main.cpp:21-46 (BLOSUM62), 87-90 (float options)
+  for (int k = 0; k < 529; ++k) p->aa_score_table[k] = (double)SK_BLOSUM62[k];
+  if (kind == SK_AA_LA || kind == SK_AA_LA_SW) {
+    p->gap = (double)-10.0f;
+    p->ext = (double)-1.0f;
     p->beta = (double)0.11f;
   }
 }
@@ -3577,7 +3832,7 @@ int sk_dataset_add(sk_dataset* ds, const char* label, int n_rows, const char* co
                    const double* const* bpp_rows, float th, int use_bp) {
   if (!ds || n_rows <= 0 || !rows) return SK_ERR_INVALID;
   if (use_bp && !bpp_rows) return SK_ERR_INVALID;
-  if (ds->uploaded) return SK_ERR_INVALID;
+  if (ds->uploaded || ds_mixes(ds, false)) return SK_ERR_INVALID;
   try {
     Example ex;
     sk::build_example(ex, n_rows, rows, bpp_rows, th, use_bp != 0);
@@ -3595,7 +3850,7 @@ int sk_dataset_add(sk_dataset* ds, const char* label, int n_rows, const char* co
 int sk_dataset_add_consensus(sk_dataset* ds, const char* label, int n_rows, const char* const* rows,
                              const double* bpp, float th) {
   if (!ds || n_rows <= 0 || !rows || !bpp) return SK_ERR_INVALID;
-  if (ds->uploaded) return SK_ERR_INVALID;
+  if (ds->uploaded || ds_mixes(ds, false)) return SK_ERR_INVALID;
   try {
     Example ex;
     sk::build_example(ex, n_rows, rows, &bpp, th, true, true);
@@ -3610,9 +3865,62 @@ int sk_dataset_add_consensus(sk_dataset* ds, const char* label, int n_rows, cons
   return SK_OK;
 }
 
+int sk_dataset_add_protein(sk_dataset* ds, const char* label, int n_rows, const char* const* rows) {
+  if (!ds || n_rows <= 0 || !rows) return SK_ERR_INVALID;
+  if (ds->uploaded || ds_mixes(ds, true)) return SK_ERR_INVALID;
+  if (n_rows >= kAaMaxRows) {
+    ds->err = "protein alignments of 4,096 rows or more are not supported";
+    return SK_ERR_UNSUPPORTED;
+  }
+  for (int r = 0; r < n_rows; ++r)
+    if (!rows[r]) return SK_ERR_INVALID;
+  try {
+    Example ex;
+    const size_t L = std::strlen(rows[0]);
+    for (int r = 1; r < n_rows; ++r)
+      if (std::strlen(rows[r]) != L) {
+        ds->err = "wrong alignment";  // bpla_kernel/data.cpp:284-288
+        return SK_ERR_INVALID;
+      }
+    ex.protein = true;
+    ex.len = (int)L;
+    ex.n_rows = n_rows;
+    ex.n_seqs = (float)n_rows;
+    ex.aa_prof.assign(L * sk::kAaSlots, 0.0f);
+    for (int r = 0; r < n_rows; ++r) {
+      ex.rows.emplace_back(rows[r]);
+      // AAProfileSequence::add_sequence, weight 1 (common/aaprofile.cpp:49-60)
+      for (size_t i = 0; i < L; ++i) ex.aa_prof[i * sk::kAaSlots + char2aa((unsigned char)rows[r][i])] += 1.0f;
+    }
+    ds->ex.push_back(std::move(ex));
+    ds->labels.emplace_back(label ? label : "");
+  } catch (const std::bad_alloc&) {
+    return SK_ERR_ALLOC;
+  }
+  return SK_OK;
+}
+
+int sk_dataset_aa_profile(const sk_dataset* ds, int i, float* prof24, float* n_seqs) {
+  if (!ds) return SK_ERR_INVALID;
+  if (i < 0 || i >= (int)ds->ex.size()) return SK_ERR_RANGE;
+  const Example& X = ds->ex[i];
+  if (!X.protein) return SK_ERR_INVALID;
+  if (prof24) std::copy(X.aa_prof.begin(), X.aa_prof.end(), prof24);
+  if (n_seqs) *n_seqs = X.n_seqs;
+  return SK_OK;
+}
+
+int sk_char2aa(int c) { return char2aa(c); }
+
+int sk_last_la_protein(const sk_context* ctx, uint32_t* mask) {
+  if (!ctx || !mask) return SK_ERR_INVALID;
+  *mask = ctx->last_la_protein;
+  return SK_OK;
+}
+
 int sk_dataset_add_copy(sk_dataset* dst, const sk_dataset* src, int32_t i) {
   if (!dst || !src || i < 0 || (size_t)i >= src->ex.size()) return SK_ERR_INVALID;
-  if (dst->uploaded) return SK_ERR_INVALID;
+  if (dst->uploaded || ds_mixes(dst, src->ex[(size_t)i].protein)) return SK_ERR_INVALID;
   try {
     dst->ex.push_back(src->ex[(size_t)i]);
     dst->labels.push_back(src->labels[(size_t)i]);
@@ -3628,12 +3936,17 @@ int sk_dataset_export(const sk_dataset* ds, int32_t first, int32_t count, uint8_
   if (!ds || !size || first < 0 || count < 0 || (size_t)first + (size_t)count > ds->ex.size())
     return SK_ERR_INVALID;
   ExWriter w{buf, buf ? cap : 0};
+  // version 2 = version 1 plus, per example, the protein fields; written only
+  // when the range holds a protein example (RNA exports stay version 1)
+  bool prot = false;
+  for (int32_t i = first; i < first + count; ++i) prot = prot || ds->ex[(size_t)i].protein;
   w.pod(kExMagic);
-  w.pod((uint32_t)1);
+  w.pod((uint32_t)(prot ? 2 : 1));
   w.pod((uint32_t)count);
   for (int32_t i = first; i < first + count; ++i) {
     w.str(ds->labels[(size_t)i]);
     example_fields(w, const_cast<Example&>(ds->ex[(size_t)i]));
+    if (prot) protein_fields(w, const_cast<Example&>(ds->ex[(size_t)i]));
   }
   *size = w.n;
   return buf && w.n > cap ? SK_ERR_RANGE : SK_OK;
@@ -3647,7 +3960,7 @@ int sk_dataset_import(sk_dataset* ds, const uint8_t* buf, size_t size) {
   r.pod(magic);
   r.pod(ver);
   r.pod(count);
-  if (!r.ok || magic != kExMagic || ver != 1) return SK_ERR_INVALID;
+  if (!r.ok || magic != kExMagic || (ver != 1 && ver != 2)) return SK_ERR_INVALID;
   std::vector<Example> ex;
   std::vector<std::string> lab;
   try {
@@ -3656,6 +3969,7 @@ int sk_dataset_import(sk_dataset* ds, const uint8_t* buf, size_t size) {
       r.str(lab.back());
       ex.emplace_back();
       example_fields(r, ex.back());
+      if (ver == 2) protein_fields(r, ex.back());
     }
   } catch (const std::bad_alloc&) {
     return SK_ERR_ALLOC;
@@ -3663,6 +3977,9 @@ int sk_dataset_import(sk_dataset* ds, const uint8_t* buf, size_t size) {
   if (!r.ok || r.n != size) return SK_ERR_INVALID;  // nothing appended from a malformed buffer
   for (const Example& X : ex)
     if (!example_valid(X)) return SK_ERR_INVALID;
+  // a dataset is RNA or protein: the buffer's examples are of one sort, the dataset's
+  for (const Example& X : ex)
+    if (X.protein != ex[0].protein || ds_mixes(ds, X.protein)) return SK_ERR_INVALID;
   try {
     ds->ex.insert(ds->ex.end(), std::make_move_iterator(ex.begin()), std::make_move_iterator(ex.end()));
     ds->labels.insert(ds->labels.end(), lab.begin(), lab.end());
@@ -3675,10 +3992,6 @@ int sk_dataset_import(sk_dataset* ds, const uint8_t* buf, size_t size) {
 int sk_dataset_pack_digest(sk_dataset* ds, uint64_t* y_hash, uint64_t* x_hash) {
   if (!ds || !y_hash || !x_hash) return SK_ERR_INVALID;
   if (ds->uploaded) return SK_ERR_INVALID;
-  std::string err;
-  const int rc = pack_dataset(ds, err);
-  if (rc) return rc;
-  const HostPack& P = ds->pack;
   auto hv = [](const auto& v, uint64_t h) {
     typedef typename std::decay_t<decltype(v)>::value_type T;
     const unsigned char* p = reinterpret_cast<const unsigned char*>(v.data());
@@ -3686,6 +3999,22 @@ int sk_dataset_pack_digest(sk_dataset* ds, uint64_t* y_hash, uint64_t* x_hash) {
     return h ^ v.size();
   };
   uint64_t hy = 1469598103934665603ull, hx = hy;
+  if (ds_protein(ds)) {  // y role: the columns; x role: the rest
+    try {
+      pack_protein(ds);
+    } catch (const std::bad_alloc&) {
+      return SK_ERR_ALLOC;
+    }
+    const sk_dataset::ProtPack& Q = ds->ppack;
+    *y_hash = hv(Q.code, hv(Q.prof, hy));
+    *x_hash = hv(Q.ex_coded, hv(Q.ex_pos_base, hv(Q.ex_len, hx)));
+    ds->ppack = sk_dataset::ProtPack();
+    return SK_OK;
+  }
+  std::string err;
+  const int rc = pack_dataset(ds, err);
+  if (rc) return rc;
+  const HostPack& P = ds->pack;
 #define SK_DG_Y(f) hy = hv(P.f, hy);
 #define SK_DG_X(f) hx = hv(P.f, hx);
   SK_PACK_Y_ARRAYS(SK_DG_Y)
@@ -3702,7 +4031,7 @@ int sk_dataset_add_synthetic_rows(sk_dataset* ds, int32_t n, int32_t n_rows,
                                   const char* const* rows, const char* const* labels, float th,
                                   int32_t n_threads) {
   if (!ds || n < 0 || n_rows < 1 || (n > 0 && !rows)) return SK_ERR_INVALID;
-  if (ds->uploaded) return SK_ERR_INVALID;
+  if (ds->uploaded || ds_mixes(ds, false)) return SK_ERR_INVALID;
   const size_t base = ds->ex.size();
   try {
     ds->ex.resize(base + n);
@@ -3869,6 +4198,26 @@ int sk_dataset_upload(sk_context* ctx, sk_dataset* ds) {
   if (!ctx || !ds) return SK_ERR_INVALID;
   if (ds->uploaded) return ds->device == ctx->device ? SK_OK : fail(ctx, SK_ERR_INVALID, "dataset bound to another device");
   SK_HIP(ctx, hipSetDevice(ctx->device));
+  if (ds_protein(ds)) {  // a protein dataset has its own image (sk::LaProtSet)
+    size_t pos = 0;
+    for (const Example& X : ds->ex) pos += (size_t)X.len;
+    if (pos > (size_t)INT32_MAX) return fail(ctx, SK_ERR_UNSUPPORTED, "protein dataset too large");
+    try {
+      pack_protein(ds);
+    } catch (const std::bad_alloc&) {
+      return fail(ctx, SK_ERR_ALLOC, "protein pack");
+    }
+    const sk_dataset::ProtPack& Q = ds->ppack;
+    SK_HIP(ctx, upload(ds->buf, Q.ex_len, &ds->pdev.ex_len));
+    SK_HIP(ctx, upload(ds->buf, Q.ex_pos_base, &ds->pdev.ex_pos_base));
+    SK_HIP(ctx, upload(ds->buf, Q.prof, &ds->pdev.prof));
+    SK_HIP(ctx, upload(ds->buf, Q.code, &ds->pdev.code));
+    ds->ppack.prof = std::vector<float>();  // (the device holds them; the host plan reads lengths and flags)
+    ds->ppack.code = std::vector<uint8_t>();
+    ds->device = ctx->device;
+    ds->uploaded = true;
+    return SK_OK;
+  }
   std::string err;
   HostPack& P = ds->pack;
   DevSet& D = ds->dev;
@@ -4401,6 +4750,7 @@ namespace {
 int add_examples_threaded(sk_dataset* ds, int32_t n, int32_t n_rows, const char* const* rows,
                           const double* const* bpp_rows, const char* const* labels, float th,
                           int use_bp, int32_t n_threads, bool consensus = false) {
+  if (ds_mixes(ds, false)) return SK_ERR_INVALID;
   const size_t base = ds->ex.size();
   try {
     ds->ex.resize(base + n);
@@ -4448,6 +4798,7 @@ int add_folded(sk_context* ctx, sk_dataset* ds, int32_t n, int32_t n_rows, const
                int32_t n_threads) {
   if (!ctx || !ds || n < 0 || n_rows < 1 || (n > 0 && !rows)) return fail(ctx, SK_ERR_INVALID, "null argument");
   if (ds->uploaded) return fail(ctx, SK_ERR_INVALID, "dataset already uploaded");
+  if (ds_mixes(ds, false)) return fail(ctx, SK_ERR_INVALID, ds->err);
   const size_t nr = (size_t)n * n_rows;
   // fold the gap-erased, lower-cased rows (common/bpmatrix.cpp:404-414)
   std::vector<std::string> erased(nr);
@@ -4491,6 +4842,7 @@ int sk_dataset_add_alifolded(sk_context* ctx, sk_dataset* ds, int32_t n, int32_t
                              int32_t fold_flags, int32_t n_threads) {
   if (!ctx || !ds || n < 0 || n_rows < 1 || (n > 0 && !rows)) return fail(ctx, SK_ERR_INVALID, "null argument");
   if (ds->uploaded) return fail(ctx, SK_ERR_INVALID, "dataset already uploaded");
+  if (ds_mixes(ds, false)) return fail(ctx, SK_ERR_INVALID, ds->err);
   // one consensus matrix per example, in alignment coordinates
   std::vector<size_t> off((size_t)n + 1, 0);
   for (int32_t i = 0; i < n; ++i) {

@@ -31,7 +31,7 @@ __all__ = [
     "fold", "random_sequences", "Dataset", "Context", "KernelMatrix",
     "SuStemKernel", "SiStemKernel", "StringKernel", "SuStemStrKernel", "StemStrKernel",
     "SiStemStrKernel", "LSuStemKernel", "LSuStemStrKernel", "NaiveStringKernel",
-    "StemKernelError", "SVMModel",
+    "StemKernelError", "SVMModel", "LAKernel",
 ]
 
 
@@ -176,6 +176,25 @@ class BPLAKernel(_Kernel):
         super().__init__(**kw)
 
 
+class LAKernel(_Kernel):
+    """BPLAKernel<double,AAMData>(score_table, noBP = true, SW, gap, ext, alpha,
+    beta): the reference's la_kernel (la_main.cpp:118-135), the local-alignment
+    kernel over protein sequences and alignments (``Dataset.add_protein``).
+
+    score_table: 23x23, [x residue][y residue] in char2aa order
+    ARNDCQEGHILKMFPSTWYVBZX (default BLOSUM62, la_main.cpp:21-46).  The CLI
+    reads gap/ext/beta as float (la_main.cpp:87-90), so they are rounded to
+    float32 here, as the CLI would."""
+
+    def __init__(self, SW=False, gap=-10.0, ext=-1.0, beta=0.11, score_table=None, cli_float=True):
+        self.kind = _lib.AA_LA_SW if SW else _lib.AA_LA
+        f = (lambda v: float(np.float32(v))) if cli_float else float
+        kw = dict(gap=f(gap), ext=f(ext), beta=f(beta))
+        if score_table is not None:
+            kw["aa_score_table"] = np.asarray(score_table, dtype=np.float64).reshape(529)
+        super().__init__(**kw)
+
+
 class StemKernel4D(_Kernel):
     """StemKernel<double,BPMat>(use_GU, loop, gap, stack, subst, band,
     ali_bound, bp_bound) of stem_kernel/ (stem_kernel.h:26-60), full_dp
@@ -290,15 +309,40 @@ class Dataset:
         rc = lib().sk_dataset_add(self._h, label.encode(), n, carr, barr, C.c_float(th), int(use_bp))
         check(rc)
 
+    def add_protein(self, label: str, rows: Sequence[str]) -> None:
+        """Append one protein example: a sequence or an alignment of
+        equal-length ``rows`` over the amino-acid alphabet
+        (sk_dataset_add_protein; AAMData(ma), bpla_kernel/data.cpp:263-293).
+        A dataset holds protein examples or RNA examples, never both."""
+        rows = [rows] if isinstance(rows, str) else list(rows)
+        n = len(rows)
+        carr = (C.c_char_p * max(n, 1))(*[r.encode() for r in rows])
+        check(lib().sk_dataset_add_protein(self._h, label.encode(), n, carr))
+
+    def aa_profile(self, i: int):
+        """AAProfileSequence columns [len][24] (counts of the 23 letters of
+        char2aa, then everything else) and n_seqs of protein example i."""
+        L = self.shape(i)[4]
+        out = np.zeros((max(L, 1), 24), np.float32)
+        ns = C.c_float()
+        check(lib().sk_dataset_aa_profile(self._h, i, out.ctypes.data_as(C.POINTER(C.c_float)),
+                                          C.byref(ns)))
+        return out[:L], ns.value
+
     def add_file(self, label: str, path: str, fmt: str = "fa", th: float = 0.01,
-                 use_bp: bool = True) -> int:
+                 use_bp: bool = True, protein: bool = False) -> int:
         """Append every example of an example file, as DataLoader<MData>
         (stem_kernel_lite/data.cpp:456-586) does for one `label file` pair of
         the CLI; each row's bpp from ``fold`` (the synthetic stand-in for
-        Vienna).  Returns the number of examples added."""
+        Vienna).  ``protein``: the rows are amino-acid rows (``add_protein``;
+        DataLoader<AAMData>, bpla_kernel/data.cpp:263-293).  Returns the
+        number of examples added."""
         alns = read_examples(path, fmt)
         for rows in alns:
-            self.add(label, rows, th=th, use_bp=use_bp)
+            if protein:
+                self.add_protein(label, rows)
+            else:
+                self.add(label, rows, th=th, use_bp=use_bp)
         return len(alns)
 
     @classmethod
@@ -744,6 +788,14 @@ class Context:
         s4d = sorted({(1 << (k & 3), bool(k & 4)) for k in range(12) if b.value >> k & 1})
         col = sorted(1 << (k & 3) for k in range(8, 12) if b.value >> k & 1)
         return dict(stem_maxk=maxk, stem4d=s4d, stem4d_col=col)
+
+    def last_la_protein(self) -> dict:
+        """Protein local-alignment kernels the last compute call launched
+        (sk_last_la_protein): ``code`` (pairs of examples with one residue
+        kind per column) and ``profile`` (the rest)."""
+        m = C.c_uint32()
+        self._chk(lib().sk_last_la_protein(self._h, C.byref(m)))
+        return dict(code=bool(m.value & 1), profile=bool(m.value & 2))
 
     def last_gamma_shared(self) -> int:
         """sk_last_gamma_shared: the class launches of the last compute call
