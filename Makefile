@@ -22,7 +22,7 @@ HIP_SRC := $(ROOT)stem_kernel_amd/csrc/kernels/dag_stem.hip $(ROOT)stem_kernel_a
            $(ROOT)stem_kernel_amd/csrc/kernels/phmm.hip $(ROOT)stem_kernel_amd/csrc/kernels/bpla_grad.hip \
            $(ROOT)stem_kernel_amd/csrc/kernels/dag_stem_big.hip $(ROOT)stem_kernel_amd/csrc/kernels/fold.hip \
            $(ROOT)stem_kernel_amd/csrc/kernels/fold_sample.hip $(ROOT)stem_kernel_amd/csrc/kernels/fold_ali.hip \
-           $(ROOT)stem_kernel_amd/csrc/kernels/la_protein.hip
+           $(ROOT)stem_kernel_amd/csrc/kernels/la_protein.hip $(ROOT)stem_kernel_amd/csrc/kernels/simpal.hip
 HDRS := $(wildcard $(ROOT)stem_kernel_amd/csrc/*/*.h) $(ROOT)include/stem_kernel.h $(ROOT)stem_kernel_amd/csrc/ribosum85_60.inc \
         $(ROOT)stem_kernel_amd/csrc/blosum62.inc
 

@@ -65,7 +65,13 @@ typedef enum {
    * instantiated at bpla_kernel.cpp:406) over protein datasets
    * (sk_dataset_add_protein): LAScore over the 23 amino-acid letters, noBP */
   SK_AA_LA = 14,       /* local_alignment_exp                                        */
-  SK_AA_LA_SW = 15     /* local_alignment_max                            --SW        */
+  SK_AA_LA_SW = 15,    /* local_alignment_max                            --SW        */
+  /* KernelFunc(tolerance) of simpal/ (simpal.cpp:225-280), the "Simple
+   * Palindrome Kernel", over palindrome datasets (sk_dataset_add_palindromes).
+   * The tolerance (allowable key mismatches, -t, default 1) is read from the
+   * mismatch field: it must be integral (else SK_ERR_INVALID), and a negative
+   * value is the reference's tolerance_ < 0: every key pair counts. */
+  SK_SIMPAL = 16
 } sk_kernel_kind;
 
 /* Kernel parameters; defaults are stem_kernel_lite/main.cpp:103-149
@@ -82,7 +88,8 @@ typedef struct {
   double alpha;       /* -a   0.2 */
   double gap;         /* -G   0.8 */
   double match;       /* --match 1.0 */
-  double mismatch;    /* --mismatch 0.8 */
+  double mismatch;    /* --mismatch 0.8; SK_SIMPAL: the tolerance -t (an integer,
+                         default 1; negative: every key pair counts) */
   double ext;         /* BPLA -e (gap extension), -0.75 */
   double score_table[16]; /* BPLA --score table, [x residue][y residue] ACGU */
   /* 4-D stem kernel (stem_kernel/main.cpp:40-60; float options): gap -g 0.8,
@@ -172,6 +179,42 @@ int sk_dataset_aa_profile(const sk_dataset *ds, int i, float *prof24, float *n_s
 /* char2aa (common/aaprofile.cpp:13-23): 0..22 for ARNDCQEGHILKMFPSTWYVBZX in
  * either case, 23 for everything else. */
 int sk_char2aa(int c);
+/* Append one palindrome example: Pals(seq, seed_length, min_loop, max_dist)
+ * of simpal/simpal.cpp:37-218 over the lowercased sequence (load_examples,
+ * :298) and its base-pairing probabilities bpp (strict upper triangle packed
+ * as in sk_dataset_add, over the n characters of seq; the reference folds with
+ * PFWrapper(seq, noGU = true), :128).  An entry per (k-mer, d): forward k-mer
+ * at i and an equal k-mer of the reversed complement at r, i and r in
+ * [0, n - seed_length) (the last k-mer is skipped, :116), d = n - i - r -
+ * 2 seed_length with min_loop <= d <= max_dist; its weight the float product
+ * of the seed_length float-rounded p(i+1+t, n-r-t), weights of one (key, d)
+ * added in float in the order increasing i, then increasing r (the reference
+ * adds them in the iteration order of a hash_multimap).  The "m\tn" lines the
+ * reference prints are not reproduced.  n < seed_length: SK_ERR_INVALID (the
+ * reference's loop bound wraps); seed_length outside 1..32:
+ * SK_ERR_UNSUPPORTED; a seed_length other than the dataset's: SK_ERR_INVALID
+ * (the reference asserts equal key lengths, :272).  A dataset is RNA, protein
+ * or palindrome, decided by its first example: mixing gives SK_ERR_INVALID,
+ * and so does SK_SIMPAL on another dataset or another kind on this one. */
+int sk_dataset_add_palindromes(sk_dataset *ds, const char *label, const char *seq,
+                               const double *bpp, int32_t seed_length, int32_t min_loop,
+                               int32_t max_dist);
+/* A palindrome example from explicit entries: keys holds n * seed_length
+ * letters of acgu, dist non-negative values, weight finite non-negative
+ * floats; anything else, and a duplicate (key, dist), is SK_ERR_INVALID.  The
+ * entries are sorted into map order (key, then dist; simpal.cpp:64-67). */
+int sk_dataset_add_palindrome_entries(sk_dataset *ds, const char *label, int32_t seed_length,
+                                      int32_t n, const char *keys, const int32_t *dist,
+                                      const float *weight);
+/* The entries of palindrome example i in map order: *n their number, keys
+ * n * seed_length letters (no terminator), dist and weight n values each
+ * (any pointer may be NULL). */
+int sk_dataset_palindromes(const sk_dataset *ds, int i, int32_t *n, char *keys, int32_t *dist,
+                           float *weight);
+/* The palindrome kernel's compile-time tile sizes (csrc/kernels/simpal.hip):
+ * y entries per LDS tile, x entries per lane (a block of x entries is 64 *
+ * x_block). */
+int sk_simpal_shape(int32_t *y_tile, int32_t *x_block);
 /* Append a copy of example i of src (its built DAG, profile and weights: no
  * rebuild) to dst, e.g. to assemble the pair a per-pair Kernel::operator()
  * call evaluates from examples built once.  dst must not be uploaded yet. */
@@ -402,6 +445,15 @@ int sk_dataset_add_consensus(sk_dataset *ds, const char *label, int n_rows,
 int sk_dataset_add_alifolded(sk_context *ctx, sk_dataset *ds, int32_t n, int32_t n_rows,
                              const char *const *rows, const char *const *labels, float th,
                              int32_t fold_flags, int32_t n_threads);
+/* n palindrome examples (sk_dataset_add_palindromes) from sequences folded
+ * with sk_fold_mccaskill(fold_flags) as they stand, lowercased; the
+ * reference's choice is SK_FOLD_NO_GU (PFWrapper(seq, true),
+ * simpal/simpal.cpp:128).  The maps are built on n_threads host threads (0 =
+ * hardware concurrency); labels may be NULL ("+1"). */
+int sk_dataset_add_palindromes_folded(sk_context *ctx, sk_dataset *ds, int32_t n,
+                                      const char *const *seqs, const char *const *labels,
+                                      int32_t fold_flags, int32_t seed_length, int32_t min_loop,
+                                      int32_t max_dist, int32_t n_threads);
 /* n examples of n_rows equal-length rows (rows[i*n_rows + r]), built on
  * n_threads host threads (0 = hardware concurrency) from the caller's
  * per-row bpp (bpp_rows[i*n_rows + r], layout of sk_dataset_add; ignored

@@ -25,7 +25,7 @@ STATUS = {
 # sk_kernel_kind
 FMT_FASTA, FMT_CLUSTAL, FMT_MAF = range(3)
 (SU_STEM, SI_STEM, SU_STR, SI_STR, SU_STEM_STR, SI_STEM_STR, LSU_STEM, LSU_STEM_STR, NAIVE_STR,
- BPLA, LA, BPLA_SW, LA_SW, STEM4D, AA_LA, AA_LA_SW) = range(16)
+ BPLA, LA, BPLA_SW, LA_SW, STEM4D, AA_LA, AA_LA_SW, SIMPAL) = range(17)
 # amino-acid letters in char2aa order (common/aaprofile.cpp:13-23); index 23 = everything else
 AA_LETTERS = "ARNDCQEGHILKMFPSTWYVBZX"
 
@@ -67,6 +67,16 @@ SIGNATURES = {
     "sk_dataset_aa_profile": (C.c_int, [_P, C.c_int, _F32P, _F32P]),
     "sk_char2aa": (C.c_int, [C.c_int]),
     "sk_last_la_protein": (C.c_int, [_P, C.POINTER(C.c_uint32)]),
+    "sk_dataset_add_palindromes": (C.c_int, [_P, C.c_char_p, C.c_char_p, C.POINTER(C.c_double),
+                                             C.c_int32, C.c_int32, C.c_int32]),
+    "sk_dataset_add_palindromes_folded": (C.c_int, [_P, _P, C.c_int32, C.POINTER(C.c_char_p),
+                                                    C.POINTER(C.c_char_p), C.c_int32, C.c_int32,
+                                                    C.c_int32, C.c_int32, C.c_int32]),
+    "sk_dataset_add_palindrome_entries": (C.c_int, [_P, C.c_char_p, C.c_int32, C.c_int32, C.c_char_p,
+                                                    C.POINTER(C.c_int32), _F32P]),
+    "sk_dataset_palindromes": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int32), C.c_char_p,
+                                         C.POINTER(C.c_int32), _F32P]),
+    "sk_simpal_shape": (C.c_int, [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "sk_dataset_size": (C.c_int, [_P]),
     "sk_dataset_add_copy": (C.c_int, [_P, _P, C.c_int32]),
     "sk_dataset_export": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t,

@@ -52,6 +52,16 @@ struct Example {
   // the RNA fields above but len, n_rows, rows and n_seqs is filled
   bool protein = false;
   std::vector<float> aa_prof;
+  // palindrome example (Pals, simpal/simpal.cpp:37-218): the map's entries in
+  // map order (key, then dist; :64-67), keys of pal_seed letters of acgu as 2
+  // bits per letter (a c g u = 0 1 2 3), first letter in the highest pair so
+  // that integer order is the strings' order; len, n_rows = 1 and rows (the
+  // lowercased sequence, empty for explicit entries) are the only other fields
+  bool pal = false;
+  int32_t pal_seed = 0;
+  std::vector<uint64_t> pal_key;
+  std::vector<int32_t> pal_dist;
+  std::vector<float> pal_w;
   int n_nodes() const { return (int)first.size(); }
   int n_edges() const { return (int)edge_to.size(); }
 };

@@ -493,4 +493,36 @@ __host__ __device__ inline size_t la_prot_prof_lds_bytes(int maxlen, int nwaves)
 hipError_t launch_la_prot_code(const LaProtLaunch& P, int grid, int nwaves, hipStream_t st);
 hipError_t launch_la_prot_prof(const LaProtLaunch& P, int grid, int nwaves, hipStream_t st);
 
+// Palindrome kernel (simpal.hip; KernelFunc::operator(), simpal/simpal.cpp:236-266).
+constexpr int kSimpalYTile = 1024;   // y entries per LDS tile
+constexpr int kSimpalXBlock = 4;     // x entries per lane (registers)
+constexpr int kSimpalWaves = 4;      // waves of a workgroup = pairs of one work item
+constexpr int kSimpalExpN = 746;     // exp(-d) != 0 for d < 746 (libm), 0 from there on
+// device image of a palindrome dataset: per example a contiguous run of
+// entries in map order
+struct SimpalSet {
+  const int32_t* ex_off = nullptr;  // [examples + 1]
+  const uint64_t* key = nullptr;    // 2 bits per letter
+  const int32_t* dist = nullptr;
+  const float* w = nullptr;
+};
+struct SimpalLaunch {
+  SimpalSet xset, yset;
+  const double* exp_tab = nullptr;  // kSimpalExpN + 1: exp(-d), the last one 0
+  int32_t tol = 0;                  // mismatches allowed (64: every key pair counts)
+  // work items: pairs [item_first[t], item_first[t + 1]) of xs / ys share their y
+  const int32_t* item_first = nullptr;
+  int32_t n_items = 0;
+  const int32_t* xs = nullptr;
+  const int32_t* ys = nullptr;
+  const int64_t* oidx = nullptr;  // out[oidx[k]] = K(pair k)
+  double* out = nullptr;
+  unsigned long long* item_counter = nullptr;
+};
+// workgroup LDS: the exp table, then one y tile as keys, weights (double) and dists
+__host__ __device__ inline size_t simpal_lds_bytes() {
+  return (size_t)(kSimpalExpN + 2) * 8 + (size_t)kSimpalYTile * (8 + 8 + 4) + 16;
+}
+hipError_t launch_simpal(const SimpalLaunch& P, int grid, hipStream_t st);
+
 }  // namespace sk

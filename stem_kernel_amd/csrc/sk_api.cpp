@@ -23,6 +23,7 @@
 #include <type_traits>
 #include <atomic>
 #include <cctype>
+#include <map>
 #include <string>
 #include <system_error>
 #include <vector>
@@ -246,6 +247,14 @@ struct sk_dataset {
     std::vector<float> prof;
   } ppack;
   sk::LaProtSet pdev;
+  // palindrome examples (sk_dataset_add_palindromes): the arrays of
+  // sk::SimpalSet, every example's entries one contiguous run
+  struct PalPack {
+    std::vector<int32_t> ex_off, dist;
+    std::vector<uint64_t> key;
+    std::vector<float> w;
+  } spack;
+  sk::SimpalSet sdev;
   std::string err;
   // x-role leaf-column closed forms (sk_prep_kernel) for one loop_gap: they
   // depend only on the dataset (immutable once uploaded) and loop_gap
@@ -257,13 +266,39 @@ struct sk_dataset {
 };
 constexpr size_t kS4Sets = 4;
 
-// A dataset is RNA or protein, decided by its first example.
+// A dataset is RNA, protein or palindrome, decided by its first example.
+enum { kSortRna = 0, kSortProtein = 1, kSortPal = 2 };
+static int ex_sort(const Example& X) { return X.pal ? kSortPal : X.protein ? kSortProtein : kSortRna; }
 static bool ds_protein(const sk_dataset* ds) { return !ds->ex.empty() && ds->ex[0].protein; }
-// appending an example of the other sort: refused (the message in ds->err)
-static bool ds_mixes(sk_dataset* ds, bool protein) {
-  if (ds->ex.empty() || ds->ex[0].protein == protein) return false;
-  ds->err = protein ? "protein example added to an RNA dataset" : "RNA example added to a protein dataset";
+static bool ds_pal(const sk_dataset* ds) { return !ds->ex.empty() && ds->ex[0].pal; }
+// appending an example of another sort: refused (the message in ds->err)
+static bool ds_mixes(sk_dataset* ds, int sort) {
+  if (ds->ex.empty() || ex_sort(ds->ex[0]) == sort) return false;
+  static const char* const name[3] = {"RNA", "protein", "palindrome"};
+  static const char* const art[3] = {"an", "a", "a"};
+  ds->err = std::string(name[sort]) + " example added to " + art[ex_sort(ds->ex[0])] + " " +
+            name[ex_sort(ds->ex[0])] + " dataset";
   return true;
+}
+// a palindrome dataset holds one seed_length (the reference asserts equal key
+// lengths, simpal/simpal.cpp:272)
+static bool pal_seed_differs(sk_dataset* ds, int32_t seed_length) {
+  if (!ds_pal(ds) || ds->ex[0].pal_seed == seed_length) return false;
+  ds->err = "palindrome example of another seed_length than the dataset's";
+  return true;
+}
+
+// Packed image of a palindrome dataset (sk::SimpalSet).
+static void pack_palindromes(sk_dataset* ds) {
+  sk_dataset::PalPack& P = ds->spack;
+  P = sk_dataset::PalPack();
+  P.ex_off.push_back(0);
+  for (const Example& X : ds->ex) {
+    P.key.insert(P.key.end(), X.pal_key.begin(), X.pal_key.end());
+    P.dist.insert(P.dist.end(), X.pal_dist.begin(), X.pal_dist.end());
+    P.w.insert(P.w.end(), X.pal_w.begin(), X.pal_w.end());
+    P.ex_off.push_back((int32_t)P.key.size());
+  }
 }
 // examples of this many rows or more are refused: below it every float
 // product and sum of LAScore's weight n is an exact integer (< 2^24)
@@ -1643,7 +1678,7 @@ bool kind_is_bpla(int k) { return k >= SK_BPLA && k <= SK_LA_SW; }
 bool kind_is_aa(int k) { return k == SK_AA_LA || k == SK_AA_LA_SW; }
 bool kind_has_stem(int k) {
   return k != SK_SU_STR && k != SK_SI_STR && k != SK_NAIVE_STR && !kind_is_bpla(k) &&
-         k != SK_STEM4D && !kind_is_aa(k);
+         k != SK_STEM4D && !kind_is_aa(k) && k != SK_SIMPAL;
 }
 bool kind_has_str(int k) {
   return k == SK_SU_STR || k == SK_SI_STR || k == SK_SU_STEM_STR || k == SK_SI_STEM_STR ||
@@ -2128,6 +2163,149 @@ int run_la_protein(sk_context* ctx, sk_dataset* xs_, sk_dataset* ys_, const sk_k
   return SK_OK;
 }
 
+// Palindrome kind (simpal.hip): the pairs grouped by their y example, each
+// group cut into work items of up to kSimpalWaves pairs, the items ordered by
+// cost |P_y| * sum |P_x| (largest first); one launch, results straight to
+// out_dev through oidx.
+int run_simpal(sk_context* ctx, sk_dataset* xs_, sk_dataset* ys_, const sk_kernel_params* kp,
+               const int32_t* x, const int32_t* y, int64_t n, double* out_dev) {
+  // the reference's int tolerance_ (simpal.cpp:231, 251): negative = every key pair counts
+  if (!(kp->mismatch == std::floor(kp->mismatch)))
+    return fail(ctx, SK_ERR_INVALID, "SK_SIMPAL: the tolerance (the mismatch field) must be an integer");
+  if (n > (int64_t)INT32_MAX - 1) return fail(ctx, SK_ERR_UNSUPPORTED, "SK_SIMPAL: too many pairs in one call");
+  if (ds_pal(xs_) && ds_pal(ys_) && xs_->ex[0].pal_seed != ys_->ex[0].pal_seed)
+    return fail(ctx, SK_ERR_INVALID, "palindrome datasets of different seed_length");
+  const int32_t tol = kp->mismatch < 0.0 ? 64 : (int32_t)std::min(kp->mismatch, 64.0);
+  const std::vector<int32_t>& OX = xs_->spack.ex_off;
+  const std::vector<int32_t>& OY = ys_->spack.ex_off;
+  // libm's exp(-d) for d = 0..745, then 0 (exp(-746.0) underflows to 0)
+  static const std::vector<double> exp_tab = [] {
+    std::vector<double> t(sk::kSimpalExpN + 1, 0.0);
+    for (int d = 0; d < sk::kSimpalExpN; ++d) t[d] = std::exp(-(double)d);
+    return t;
+  }();
+  const size_t nb = (size_t)n;
+  // the pairs grouped by y (a counting sort), inside a group by |P_x|,
+  // largest first, then by their place in the call
+  auto px_n = [&](int32_t k) { return OX[x[k] + 1] - OX[x[k]]; };
+  const size_t n_y = ys_->ex.size();
+  std::vector<int32_t> ord(nb);
+  {
+    std::vector<size_t> start(n_y + 1, 0);
+    for (size_t k = 0; k < nb; ++k) ++start[(size_t)y[k] + 1];
+    for (size_t g = 0; g < n_y; ++g) start[g + 1] += start[g];
+    std::vector<size_t> fill(start.begin(), start.end() - 1);
+    std::vector<uint64_t> key(nb);
+    for (size_t k = 0; k < nb; ++k)
+      key[fill[(size_t)y[k]]++] = (uint64_t)(0xffffffffu - (uint32_t)px_n((int32_t)k)) << 32 | (uint32_t)k;
+    for (size_t g = 0; g < n_y; ++g)
+      if (start[g + 1] - start[g] > 1) std::sort(key.begin() + start[g], key.begin() + start[g + 1]);
+    for (size_t k = 0; k < nb; ++k) ord[k] = (int32_t)(key[k] & 0xffffffffu);
+  }
+  struct Item {
+    int32_t first, count;
+    double cost;
+  };
+  std::vector<Item> items;
+  double terms = 0.0;
+  for (size_t k = 0; k < nb;) {
+    size_t e = k;
+    double sx = 0.0;
+    while (e < nb && e - k < (size_t)sk::kSimpalWaves && y[ord[e]] == y[ord[k]]) sx += (double)px_n(ord[e++]);
+    const double c = sx * (double)(OY[y[ord[k]] + 1] - OY[y[ord[k]]]);
+    items.push_back(Item{(int32_t)k, (int32_t)(e - k), c});
+    terms += c;
+    k = e;
+  }
+  ctx->last_cells = terms;
+  std::stable_sort(items.begin(), items.end(), [](const Item& a, const Item& b) { return a.cost > b.cost; });
+  const size_t ni = items.size();
+  std::vector<int32_t> px(nb), py(nb), ifirst(ni + 1);
+  std::vector<int64_t> oidx(nb);
+  {
+    size_t d = 0;
+    for (size_t t = 0; t < ni; ++t) {
+      ifirst[t] = (int32_t)d;
+      for (int32_t q = 0; q < items[t].count; ++q, ++d) {
+        const int32_t k = ord[(size_t)items[t].first + q];
+        px[d] = x[k];
+        py[d] = y[k];
+        oidx[d] = k;
+      }
+    }
+    ifirst[ni] = (int32_t)d;
+  }
+  const size_t ne = exp_tab.size();
+  int rc = ensure_work(ctx, ne * 8 + 64 + nb * 16 + (ni + 1) * 4 + 8192);
+  if (rc) return rc;
+  // the call's inputs and the zeroed counter go up in one copy (run_bpla)
+  double* d_tb;
+  unsigned long long* d_ctr;
+  int32_t *d_px, *d_py, *d_if;
+  int64_t* d_oidx;
+  auto lay = [&](Arena& U) {
+    d_tb = U.take<double>(ne);
+    d_ctr = U.take<unsigned long long>(8);
+    d_px = U.take<int32_t>(nb);
+    d_py = U.take<int32_t>(nb);
+    d_if = U.take<int32_t>(ni + 1);
+    d_oidx = U.take<int64_t>(nb);
+  };
+  Arena A{static_cast<char*>(ctx->work), 0, ctx->work_bytes};
+  Arena U{nullptr, 0, 0};
+  lay(U);  // (sizes only)
+  const size_t up_bytes = U.off;
+  if (ctx->async) {
+    char* ub = nullptr;
+    SK_HIP(ctx, sk::up_reserve(ctx, up_bytes, &ub));
+    U = Arena{ub, 0, up_bytes};
+    lay(U);
+  } else {
+    lay(A);
+    U.base = A.base;
+  }
+  hipStream_t S = ctx->stream;
+  {
+    thread_local std::vector<char> hb;
+    hb.assign(up_bytes, 0);
+    auto put = [&](const void* dptr, const void* src, size_t bytes) {
+      if (bytes) std::memcpy(hb.data() + (static_cast<const char*>(dptr) - U.base), src, bytes);
+    };
+    put(d_tb, exp_tab.data(), ne * 8);
+    put(d_px, px.data(), nb * 4);
+    put(d_py, py.data(), nb * 4);
+    put(d_if, ifirst.data(), (ni + 1) * 4);
+    put(d_oidx, oidx.data(), nb * 8);
+    if (ctx->async)
+      SK_HIP(ctx, sk::up_copy(ctx, hb.data(), up_bytes, S));
+    else
+      SK_HIP(ctx, sk::h2d(ctx, U.base, hb.data(), up_bytes, S));
+  }
+  sk::SimpalLaunch T;
+  T.xset = xs_->sdev;
+  T.yset = ys_->sdev;
+  T.exp_tab = d_tb;
+  T.tol = tol;
+  T.item_first = d_if;
+  T.n_items = (int32_t)ni;
+  T.xs = d_px;
+  T.ys = d_py;
+  T.oidx = d_oidx;
+  T.out = out_dev;
+  T.item_counter = d_ctr;
+  // four workgroups of kSimpalWaves waves per CU (4 waves per SIMD; their
+  // LDS, 26.5 KB each, fits a CU's 160 KB)
+  const int64_t g = std::min<int64_t>((int64_t)ctx->n_cu * 4, (int64_t)ni);
+  SK_HIP(ctx, hipEventRecord(ctx->ev0, S));
+  SK_HIP(ctx, sk::lev_mark(ctx, S));
+  SK_HIP(ctx, sk::launch_simpal(T, (int)g, S));
+  SK_HIP(ctx, sk::lev_mark(ctx, S));
+  SK_HIP(ctx, hipEventRecord(ctx->ev1, S));
+  ctx->last_launches = 1;
+  SK_HIP(ctx, sk::call_finish(ctx, S, true, false));
+  return SK_OK;
+}
+
 // 4-D stem kernel: per example, the lowercased sequence (the loader's
 // ToLower, common/example.cpp:26-34) and BPMat::prob(a, b) for a <= b by
 // diagonal e = b - a (prob(a,a) = 0), as float (stem_kernel.cpp:320, 328).
@@ -2562,8 +2740,15 @@ int run_pairs(sk_context* ctx, sk_dataset* xs_, sk_dataset* ys_, const sk_kernel
   rc = check_set(ctx, ys_);
   if (rc) return rc;
   if (n < 0) return fail(ctx, SK_ERR_INVALID, "negative pair count");
-  if (kp->kind < SK_SU_STEM || kp->kind > SK_AA_LA_SW)
+  if (kp->kind < SK_SU_STEM || kp->kind > SK_SIMPAL)
     return fail(ctx, SK_ERR_UNSUPPORTED, "unknown kernel kind");
+  // palindrome datasets and SK_SIMPAL go together, and with nothing else
+  if (ds_pal(xs_) != ds_pal(ys_) && !xs_->ex.empty() && !ys_->ex.empty())
+    return fail(ctx, SK_ERR_INVALID, "a palindrome dataset paired with a dataset of another sort");
+  if (kp->kind == SK_SIMPAL && !(ds_pal(xs_) && ds_pal(ys_)) && n > 0)
+    return fail(ctx, SK_ERR_INVALID, "the palindrome kernel kind (SK_SIMPAL) needs palindrome datasets (sk_dataset_add_palindromes)");
+  if (kp->kind != SK_SIMPAL && (ds_pal(xs_) || ds_pal(ys_)))
+    return fail(ctx, SK_ERR_INVALID, "a kernel kind other than SK_SIMPAL on a palindrome dataset");
   // no silent reinterpretation of one alphabet as the other
   if (ds_protein(xs_) != ds_protein(ys_) && !xs_->ex.empty() && !ys_->ex.empty())
     return fail(ctx, SK_ERR_INVALID, "a protein dataset paired with an RNA dataset");
@@ -2585,6 +2770,7 @@ int run_pairs(sk_context* ctx, sk_dataset* xs_, sk_dataset* ys_, const sk_kernel
   SK_HIP(ctx, sk::call_begin(ctx));
   if (kind_is_bpla(kp->kind)) return run_bpla(ctx, xs_, ys_, kp, x, y, n, out_dev);
   if (kind_is_aa(kp->kind)) return run_la_protein(ctx, xs_, ys_, kp, x, y, n, out_dev);
+  if (kp->kind == SK_SIMPAL) return run_simpal(ctx, xs_, ys_, kp, x, y, n, out_dev);
   if (kp->kind == SK_STEM4D) {
     // synchronous batches (each waits for its spans): its totals are final
     rc = run_stem4d(ctx, xs_, ys_, kp, x, y, n, out_dev);
@@ -3300,6 +3486,8 @@ int bpla_gradients(sk_context* ctx, sk_dataset* xs_, sk_dataset* ys_, const sk_k
   if (rc) return rc;
   if (ds_protein(xs_) || ds_protein(ys_))
     return fail(ctx, SK_ERR_INVALID, "BPLA gradients on a protein dataset");
+  if (ds_pal(xs_) || ds_pal(ys_))
+    return fail(ctx, SK_ERR_INVALID, "BPLA gradients on a palindrome dataset");
   if (n <= 0) return n < 0 ? fail(ctx, SK_ERR_INVALID, "negative pair count") : SK_OK;
   SK_HIP(ctx, sk::call_begin(ctx));  // (synchronous: a fresh timing set, not a pending one)
   for (int64_t k = 0; k < n; ++k) {
@@ -3623,7 +3811,34 @@ void protein_fields(IO& io, E& X) {
   if constexpr (std::is_same_v<IO, ExReader>) X.protein = pb != 0;
   io.vec(X.aa_prof);
 }
+template <class IO, class E>
+void palindrome_fields(IO& io, E& X) {
+  uint8_t pb = X.pal ? 1 : 0;
+  io.pod(pb);
+  if constexpr (std::is_same_v<IO, ExReader>) X.pal = pb != 0;
+  io.pod(X.pal_seed);
+  io.vec(X.pal_key);
+  io.vec(X.pal_dist);
+  io.vec(X.pal_w);
+}
 constexpr uint32_t kExMagic = 0x58454b53u;  // "SKEX"
+
+// What simpal.hip relies on in a palindrome example: entries in map order
+// without duplicates, keys of seed_length letters, dists >= 0, finite
+// weights >= 0.
+bool palindromes_valid(const Example& X) {
+  const size_t m = X.pal_key.size();
+  if (X.pal_seed < 1 || X.pal_seed > 32 || X.pal_dist.size() != m || X.pal_w.size() != m) return false;
+  if (m > (size_t)INT32_MAX) return false;
+  for (size_t k = 0; k < m; ++k) {
+    if (X.pal_seed < 32 && (X.pal_key[k] >> (2 * X.pal_seed)) != 0) return false;
+    if (X.pal_dist[k] < 0 || !(X.pal_w[k] >= 0.0f) || !std::isfinite(X.pal_w[k])) return false;
+    if (k && !(X.pal_key[k - 1] < X.pal_key[k] ||
+               (X.pal_key[k - 1] == X.pal_key[k] && X.pal_dist[k - 1] < X.pal_dist[k])))
+      return false;
+  }
+  return true;
+}
 
 // The invariants example_build.cpp establishes and the packer and kernels
 // rely on (sizes, offsets, children numbered before parents, positions and
@@ -3633,6 +3848,13 @@ bool example_valid(const Example& X) {
   if (X.len < 0 || X.n_rows < 1 || X.rows.size() != (size_t)X.n_rows) return false;
   for (const auto& r : X.rows)
     if (r.size() != L) return false;
+  const bool no_rna = !X.has_bp && X.prof5.empty() && X.pos_weight.empty() && X.bpp.empty() && X.first.empty() &&
+                      X.last.empty() && X.weight.empty() && X.edge_off.empty() && X.edge_to.empty() &&
+                      X.edge_gaps.empty() && X.bpf_off.empty() && X.bpf_code.empty() && X.bpf_p.empty() &&
+                      X.roots.empty() && X.max_pa.empty();
+  if (X.pal)  // its entries, and none of the RNA or protein fields
+    return !X.protein && X.aa_prof.empty() && X.n_rows == 1 && no_rna && palindromes_valid(X);
+  if (X.pal_seed != 0 || !X.pal_key.empty() || !X.pal_dist.empty() || !X.pal_w.empty()) return false;
   if (X.protein) {
     // integer counts, every column summing to the row count (< 4,096 rows),
     // and none of the RNA fields
@@ -3724,6 +3946,8 @@ void sk_kernel_params_default(sk_kernel_params* p, int32_t kind) {
     p->ext = (double)-1.0f;
     p->beta = (double)0.11f;
   }
+  // simpal/simpal.cpp:316, 335: tolerance 1, carried by the mismatch field
+  if (kind == SK_SIMPAL) p->mismatch = 1.0;
 }
 
 const char* sk_strerror(int s) {
@@ -3832,7 +4056,7 @@ int sk_dataset_add(sk_dataset* ds, const char* label, int n_rows, const char* co
                    const double* const* bpp_rows, float th, int use_bp) {
   if (!ds || n_rows <= 0 || !rows) return SK_ERR_INVALID;
   if (use_bp && !bpp_rows) return SK_ERR_INVALID;
-  if (ds->uploaded || ds_mixes(ds, false)) return SK_ERR_INVALID;
+  if (ds->uploaded || ds_mixes(ds, kSortRna)) return SK_ERR_INVALID;
   try {
     Example ex;
     sk::build_example(ex, n_rows, rows, bpp_rows, th, use_bp != 0);
@@ -3850,7 +4074,7 @@ int sk_dataset_add(sk_dataset* ds, const char* label, int n_rows, const char* co
 int sk_dataset_add_consensus(sk_dataset* ds, const char* label, int n_rows, const char* const* rows,
                              const double* bpp, float th) {
   if (!ds || n_rows <= 0 || !rows || !bpp) return SK_ERR_INVALID;
-  if (ds->uploaded || ds_mixes(ds, false)) return SK_ERR_INVALID;
+  if (ds->uploaded || ds_mixes(ds, kSortRna)) return SK_ERR_INVALID;
   try {
     Example ex;
     sk::build_example(ex, n_rows, rows, &bpp, th, true, true);
@@ -3867,7 +4091,7 @@ int sk_dataset_add_consensus(sk_dataset* ds, const char* label, int n_rows, cons
 
 int sk_dataset_add_protein(sk_dataset* ds, const char* label, int n_rows, const char* const* rows) {
   if (!ds || n_rows <= 0 || !rows) return SK_ERR_INVALID;
-  if (ds->uploaded || ds_mixes(ds, true)) return SK_ERR_INVALID;
+  if (ds->uploaded || ds_mixes(ds, kSortProtein)) return SK_ERR_INVALID;
   if (n_rows >= kAaMaxRows) {
     ds->err = "protein alignments of 4,096 rows or more are not supported";
     return SK_ERR_UNSUPPORTED;
@@ -3918,9 +4142,221 @@ int sk_last_la_protein(const sk_context* ctx, uint32_t* mask) {
   return SK_OK;
 }
 
+}  // extern "C"
+
+namespace {
+// a c g u -> 0 1 2 3 (the strings' order), anything else -1
+int pal_code(char c) {
+  switch (c) {
+    case 'a': return 0;
+    case 'c': return 1;
+    case 'g': return 2;
+    case 'u': return 3;
+    default: return -1;
+  }
+}
+// arguments the builders refuse; the message in *err
+int pal_args(size_t n, int32_t seed_length, int32_t min_loop, int32_t max_dist, std::string* err) {
+  if (seed_length < 1 || seed_length > 32) {
+    *err = "palindrome seed_length outside 1..32";
+    return SK_ERR_UNSUPPORTED;
+  }
+  if (min_loop < 0 || max_dist < 0) {
+    *err = "negative min_loop or max_dist";
+    return SK_ERR_INVALID;
+  }
+  if (n < (size_t)seed_length) {  // the reference's loop bound wraps (simpal.cpp:116)
+    *err = "sequence shorter than seed_length";
+    return SK_ERR_INVALID;
+  }
+  return SK_OK;
+}
+// Pals::make_pal_map (simpal/simpal.cpp:101-218) over the lowercased
+// sequence seq and its bpp (packed strict upper, double).  Same (key, d)
+// weights are added in float in the order increasing i, then increasing r.
+void build_palindromes(Example& ex, const std::string& seq, const double* bpp, int32_t s, int32_t min_loop,
+                       int32_t max_dist) {
+  const int n = (int)seq.size();
+  ex = Example();
+  ex.pal = true;
+  ex.pal_seed = s;
+  ex.len = n;
+  ex.n_rows = 1;
+  ex.n_seqs = 1.0f;
+  ex.rows.assign(1, seq);
+  // k-mers i in [0, n - s) (the last one is skipped, :116) as 2-bit words,
+  // forward and of the reversed complement (RevComp, :73-95: t pairs as u,
+  // anything else maps to NUL and never matches)
+  const int nk = n - s;
+  const size_t nks = (size_t)std::max(nk, 0);
+  std::vector<uint64_t> fk(nks), rk(nks);
+  std::vector<uint8_t> fok(nks), rok(nks);
+  auto comp = [](char c) {
+    switch (c) {
+      case 'a': return 3;
+      case 'c': return 2;
+      case 'g': return 1;
+      case 'u':
+      case 't': return 0;
+      default: return -1;
+    }
+  };
+  for (int i = 0; i < nk; ++i) {
+    uint64_t kf = 0, kr = 0;
+    bool okf = true, okr = true;
+    for (int t = 0; t < s; ++t) {
+      const int a = pal_code(seq[(size_t)(i + t)]), b = comp(seq[(size_t)(n - 1 - i - t)]);
+      okf = okf && a >= 0;
+      okr = okr && b >= 0;
+      kf = (kf << 2) | (uint64_t)(a & 3);
+      kr = (kr << 2) | (uint64_t)(b & 3);
+    }
+    fk[(size_t)i] = kf;
+    rk[(size_t)i] = kr;
+    fok[(size_t)i] = okf;
+    rok[(size_t)i] = okr;
+  }
+  std::map<std::pair<uint64_t, int32_t>, float> pals;
+  for (int i = 0; i < nk; ++i) {
+    if (!fok[(size_t)i]) continue;
+    for (int r = 0; r < nk; ++r) {
+      if (!rok[(size_t)r] || rk[(size_t)r] != fk[(size_t)i]) continue;
+      const int d = n - i - r - 2 * s;  // unsigned in the reference (:152): negative fails
+      if (d < min_loop || d > max_dist) continue;
+      float weight = 1.0f;
+      for (int t = 0; t < s; ++t) {
+        // pf(m, n) with m = i + 1 + t < n = len - r - t, 1-based (:170-171),
+        // the double rounded to float (PFWrapper::operator(), pf_wrapper.h:41-44)
+        const float p = (float)bpp[sk::tri_index(n, i + t, n - r - t - 1)];
+        weight = p * weight;
+      }
+      auto it = pals.find(std::make_pair(fk[(size_t)i], (int32_t)d));
+      if (it == pals.end())
+        pals.emplace(std::make_pair(fk[(size_t)i], (int32_t)d), weight);
+      else
+        it->second += weight;
+    }
+  }
+  for (const auto& e : pals) {
+    ex.pal_key.push_back(e.first.first);
+    ex.pal_dist.push_back(e.first.second);
+    ex.pal_w.push_back(e.second);
+  }
+}
+std::string lower(const char* s) {
+  std::string o(s);
+  for (char& c : o) c = (char)std::tolower((unsigned char)c);
+  return o;
+}
+}  // namespace
+
+extern "C" {
+
+int sk_dataset_add_palindromes(sk_dataset* ds, const char* label, const char* seq, const double* bpp,
+                               int32_t seed_length, int32_t min_loop, int32_t max_dist) {
+  if (!ds || !seq) return SK_ERR_INVALID;
+  if (ds->uploaded || ds_mixes(ds, kSortPal)) return SK_ERR_INVALID;
+  try {
+    const std::string sq = lower(seq);
+    const int rc = pal_args(sq.size(), seed_length, min_loop, max_dist, &ds->err);
+    if (rc) return rc;
+    if (pal_seed_differs(ds, seed_length)) return SK_ERR_INVALID;
+    if (!bpp && sq.size() > 1) return SK_ERR_INVALID;
+    Example ex;
+    build_palindromes(ex, sq, bpp, seed_length, min_loop, max_dist);
+    ds->ex.push_back(std::move(ex));
+    ds->labels.emplace_back(label ? label : "");
+  } catch (const std::bad_alloc&) {
+    return SK_ERR_ALLOC;
+  }
+  return SK_OK;
+}
+
+int sk_dataset_add_palindrome_entries(sk_dataset* ds, const char* label, int32_t seed_length, int32_t n,
+                                      const char* keys, const int32_t* dist, const float* weight) {
+  if (!ds || n < 0 || (n > 0 && (!keys || !dist || !weight))) return SK_ERR_INVALID;
+  if (ds->uploaded || ds_mixes(ds, kSortPal)) return SK_ERR_INVALID;
+  if (seed_length < 1 || seed_length > 32) {
+    ds->err = "palindrome seed_length outside 1..32";
+    return SK_ERR_UNSUPPORTED;
+  }
+  if (pal_seed_differs(ds, seed_length)) return SK_ERR_INVALID;
+  try {
+    struct Ent {
+      uint64_t key;
+      int32_t dist;
+      float w;
+    };
+    std::vector<Ent> v((size_t)n);
+    for (int32_t k = 0; k < n; ++k) {
+      uint64_t key = 0;
+      for (int t = 0; t < seed_length; ++t) {
+        const int c = pal_code(keys[(size_t)k * seed_length + t]);
+        if (c < 0) {
+          ds->err = "palindrome key letter outside acgu";
+          return SK_ERR_INVALID;
+        }
+        key = (key << 2) | (uint64_t)c;
+      }
+      if (dist[k] < 0 || !(weight[k] >= 0.0f) || !std::isfinite(weight[k])) {
+        ds->err = "palindrome entry with a negative dist or a weight that is not finite and non-negative";
+        return SK_ERR_INVALID;
+      }
+      v[(size_t)k] = Ent{key, dist[k], weight[k]};
+    }
+    std::sort(v.begin(), v.end(),
+              [](const Ent& a, const Ent& b) { return a.key != b.key ? a.key < b.key : a.dist < b.dist; });
+    for (size_t k = 1; k < v.size(); ++k)
+      if (v[k].key == v[k - 1].key && v[k].dist == v[k - 1].dist) {
+        ds->err = "duplicate palindrome entry (key, dist)";
+        return SK_ERR_INVALID;
+      }
+    Example ex;
+    ex.pal = true;
+    ex.pal_seed = seed_length;
+    ex.n_rows = 1;
+    ex.n_seqs = 1.0f;
+    ex.rows.assign(1, std::string());
+    for (const Ent& e : v) {
+      ex.pal_key.push_back(e.key);
+      ex.pal_dist.push_back(e.dist);
+      ex.pal_w.push_back(e.w);
+    }
+    ds->ex.push_back(std::move(ex));
+    ds->labels.emplace_back(label ? label : "");
+  } catch (const std::bad_alloc&) {
+    return SK_ERR_ALLOC;
+  }
+  return SK_OK;
+}
+
+int sk_dataset_palindromes(const sk_dataset* ds, int i, int32_t* n, char* keys, int32_t* dist, float* weight) {
+  if (!ds) return SK_ERR_INVALID;
+  if (i < 0 || i >= (int)ds->ex.size()) return SK_ERR_RANGE;
+  const Example& X = ds->ex[i];
+  if (!X.pal) return SK_ERR_INVALID;
+  const size_t m = X.pal_key.size();
+  if (n) *n = (int32_t)m;
+  if (keys)
+    for (size_t k = 0; k < m; ++k)
+      for (int t = 0; t < X.pal_seed; ++t)
+        keys[k * X.pal_seed + t] = "acgu"[(X.pal_key[k] >> (2 * (X.pal_seed - 1 - t))) & 3];
+  if (dist) std::copy(X.pal_dist.begin(), X.pal_dist.end(), dist);
+  if (weight) std::copy(X.pal_w.begin(), X.pal_w.end(), weight);
+  return SK_OK;
+}
+
+int sk_simpal_shape(int32_t* y_tile, int32_t* x_block) {
+  if (y_tile) *y_tile = sk::kSimpalYTile;
+  if (x_block) *x_block = sk::kSimpalXBlock;
+  return SK_OK;
+}
+
 int sk_dataset_add_copy(sk_dataset* dst, const sk_dataset* src, int32_t i) {
   if (!dst || !src || i < 0 || (size_t)i >= src->ex.size()) return SK_ERR_INVALID;
-  if (dst->uploaded || ds_mixes(dst, src->ex[(size_t)i].protein)) return SK_ERR_INVALID;
+  if (dst->uploaded || ds_mixes(dst, ex_sort(src->ex[(size_t)i])) ||
+      (src->ex[(size_t)i].pal && pal_seed_differs(dst, src->ex[(size_t)i].pal_seed)))
+    return SK_ERR_INVALID;
   try {
     dst->ex.push_back(src->ex[(size_t)i]);
     dst->labels.push_back(src->labels[(size_t)i]);
@@ -3938,15 +4374,22 @@ int sk_dataset_export(const sk_dataset* ds, int32_t first, int32_t count, uint8_
   ExWriter w{buf, buf ? cap : 0};
   // version 2 = version 1 plus, per example, the protein fields; written only
   // when the range holds a protein example (RNA exports stay version 1)
-  bool prot = false;
-  for (int32_t i = first; i < first + count; ++i) prot = prot || ds->ex[(size_t)i].protein;
+  // version 3 = version 2 plus, per example, the palindrome fields; written
+  // only when the range holds a palindrome example
+  bool prot = false, pal = false;
+  for (int32_t i = first; i < first + count; ++i) {
+    prot = prot || ds->ex[(size_t)i].protein;
+    pal = pal || ds->ex[(size_t)i].pal;
+  }
+  prot = prot || pal;
   w.pod(kExMagic);
-  w.pod((uint32_t)(prot ? 2 : 1));
+  w.pod((uint32_t)(pal ? 3 : prot ? 2 : 1));
   w.pod((uint32_t)count);
   for (int32_t i = first; i < first + count; ++i) {
     w.str(ds->labels[(size_t)i]);
     example_fields(w, const_cast<Example&>(ds->ex[(size_t)i]));
     if (prot) protein_fields(w, const_cast<Example&>(ds->ex[(size_t)i]));
+    if (pal) palindrome_fields(w, const_cast<Example&>(ds->ex[(size_t)i]));
   }
   *size = w.n;
   return buf && w.n > cap ? SK_ERR_RANGE : SK_OK;
@@ -3960,7 +4403,7 @@ int sk_dataset_import(sk_dataset* ds, const uint8_t* buf, size_t size) {
   r.pod(magic);
   r.pod(ver);
   r.pod(count);
-  if (!r.ok || magic != kExMagic || (ver != 1 && ver != 2)) return SK_ERR_INVALID;
+  if (!r.ok || magic != kExMagic || ver < 1 || ver > 3) return SK_ERR_INVALID;
   std::vector<Example> ex;
   std::vector<std::string> lab;
   try {
@@ -3969,7 +4412,8 @@ int sk_dataset_import(sk_dataset* ds, const uint8_t* buf, size_t size) {
       r.str(lab.back());
       ex.emplace_back();
       example_fields(r, ex.back());
-      if (ver == 2) protein_fields(r, ex.back());
+      if (ver >= 2) protein_fields(r, ex.back());
+      if (ver == 3) palindrome_fields(r, ex.back());
     }
   } catch (const std::bad_alloc&) {
     return SK_ERR_ALLOC;
@@ -3977,9 +4421,12 @@ int sk_dataset_import(sk_dataset* ds, const uint8_t* buf, size_t size) {
   if (!r.ok || r.n != size) return SK_ERR_INVALID;  // nothing appended from a malformed buffer
   for (const Example& X : ex)
     if (!example_valid(X)) return SK_ERR_INVALID;
-  // a dataset is RNA or protein: the buffer's examples are of one sort, the dataset's
+  // a dataset is of one sort (and, palindromes, one seed_length): the
+  // buffer's examples are of one sort, the dataset's
   for (const Example& X : ex)
-    if (X.protein != ex[0].protein || ds_mixes(ds, X.protein)) return SK_ERR_INVALID;
+    if (ex_sort(X) != ex_sort(ex[0]) || ds_mixes(ds, ex_sort(X)) ||
+        (X.pal && (X.pal_seed != ex[0].pal_seed || pal_seed_differs(ds, X.pal_seed))))
+      return SK_ERR_INVALID;
   try {
     ds->ex.insert(ds->ex.end(), std::make_move_iterator(ex.begin()), std::make_move_iterator(ex.end()));
     ds->labels.insert(ds->labels.end(), lab.begin(), lab.end());
@@ -3999,6 +4446,18 @@ int sk_dataset_pack_digest(sk_dataset* ds, uint64_t* y_hash, uint64_t* x_hash) {
     return h ^ v.size();
   };
   uint64_t hy = 1469598103934665603ull, hx = hy;
+  if (ds_pal(ds)) {  // y role: the entries; x role: the runs
+    try {
+      pack_palindromes(ds);
+    } catch (const std::bad_alloc&) {
+      return SK_ERR_ALLOC;
+    }
+    const sk_dataset::PalPack& Q = ds->spack;
+    *y_hash = hv(Q.w, hv(Q.dist, hv(Q.key, hy)));
+    *x_hash = hv(Q.ex_off, hx);
+    ds->spack = sk_dataset::PalPack();
+    return SK_OK;
+  }
   if (ds_protein(ds)) {  // y role: the columns; x role: the rest
     try {
       pack_protein(ds);
@@ -4031,7 +4490,7 @@ int sk_dataset_add_synthetic_rows(sk_dataset* ds, int32_t n, int32_t n_rows,
                                   const char* const* rows, const char* const* labels, float th,
                                   int32_t n_threads) {
   if (!ds || n < 0 || n_rows < 1 || (n > 0 && !rows)) return SK_ERR_INVALID;
-  if (ds->uploaded || ds_mixes(ds, false)) return SK_ERR_INVALID;
+  if (ds->uploaded || ds_mixes(ds, kSortRna)) return SK_ERR_INVALID;
   const size_t base = ds->ex.size();
   try {
     ds->ex.resize(base + n);
@@ -4198,6 +4657,27 @@ int sk_dataset_upload(sk_context* ctx, sk_dataset* ds) {
   if (!ctx || !ds) return SK_ERR_INVALID;
   if (ds->uploaded) return ds->device == ctx->device ? SK_OK : fail(ctx, SK_ERR_INVALID, "dataset bound to another device");
   SK_HIP(ctx, hipSetDevice(ctx->device));
+  if (ds_pal(ds)) {  // a palindrome dataset has its own image (sk::SimpalSet)
+    size_t m = 0;
+    for (const Example& X : ds->ex) m += X.pal_key.size();
+    if (m > (size_t)INT32_MAX) return fail(ctx, SK_ERR_UNSUPPORTED, "palindrome dataset too large");
+    try {
+      pack_palindromes(ds);
+    } catch (const std::bad_alloc&) {
+      return fail(ctx, SK_ERR_ALLOC, "palindrome pack");
+    }
+    const sk_dataset::PalPack& Q = ds->spack;
+    SK_HIP(ctx, upload(ds->buf, Q.ex_off, &ds->sdev.ex_off));
+    SK_HIP(ctx, upload(ds->buf, Q.key, &ds->sdev.key));
+    SK_HIP(ctx, upload(ds->buf, Q.dist, &ds->sdev.dist));
+    SK_HIP(ctx, upload(ds->buf, Q.w, &ds->sdev.w));
+    ds->spack.key = std::vector<uint64_t>();  // (the device holds them; the host plan reads the offsets)
+    ds->spack.dist = std::vector<int32_t>();
+    ds->spack.w = std::vector<float>();
+    ds->device = ctx->device;
+    ds->uploaded = true;
+    return SK_OK;
+  }
   if (ds_protein(ds)) {  // a protein dataset has its own image (sk::LaProtSet)
     size_t pos = 0;
     for (const Example& X : ds->ex) pos += (size_t)X.len;
@@ -4750,7 +5230,7 @@ namespace {
 int add_examples_threaded(sk_dataset* ds, int32_t n, int32_t n_rows, const char* const* rows,
                           const double* const* bpp_rows, const char* const* labels, float th,
                           int use_bp, int32_t n_threads, bool consensus = false) {
-  if (ds_mixes(ds, false)) return SK_ERR_INVALID;
+  if (ds_mixes(ds, kSortRna)) return SK_ERR_INVALID;
   const size_t base = ds->ex.size();
   try {
     ds->ex.resize(base + n);
@@ -4798,7 +5278,7 @@ int add_folded(sk_context* ctx, sk_dataset* ds, int32_t n, int32_t n_rows, const
                int32_t n_threads) {
   if (!ctx || !ds || n < 0 || n_rows < 1 || (n > 0 && !rows)) return fail(ctx, SK_ERR_INVALID, "null argument");
   if (ds->uploaded) return fail(ctx, SK_ERR_INVALID, "dataset already uploaded");
-  if (ds_mixes(ds, false)) return fail(ctx, SK_ERR_INVALID, ds->err);
+  if (ds_mixes(ds, kSortRna)) return fail(ctx, SK_ERR_INVALID, ds->err);
   const size_t nr = (size_t)n * n_rows;
   // fold the gap-erased, lower-cased rows (common/bpmatrix.cpp:404-414)
   std::vector<std::string> erased(nr);
@@ -4842,7 +5322,7 @@ int sk_dataset_add_alifolded(sk_context* ctx, sk_dataset* ds, int32_t n, int32_t
                              int32_t fold_flags, int32_t n_threads) {
   if (!ctx || !ds || n < 0 || n_rows < 1 || (n > 0 && !rows)) return fail(ctx, SK_ERR_INVALID, "null argument");
   if (ds->uploaded) return fail(ctx, SK_ERR_INVALID, "dataset already uploaded");
-  if (ds_mixes(ds, false)) return fail(ctx, SK_ERR_INVALID, ds->err);
+  if (ds_mixes(ds, kSortRna)) return fail(ctx, SK_ERR_INVALID, ds->err);
   // one consensus matrix per example, in alignment coordinates
   std::vector<size_t> off((size_t)n + 1, 0);
   for (int32_t i = 0; i < n; ++i) {
@@ -4858,6 +5338,60 @@ int sk_dataset_add_alifolded(sk_context* ctx, sk_dataset* ds, int32_t n, int32_t
   for (int32_t i = 0; i < n; ++i) bptr[i] = bpp.data() + off[i];
   rc = add_examples_threaded(ds, n, n_rows, rows, bptr.data(), labels, th, 1, n_threads, true);
   return rc ? fail(ctx, rc, "example build failed") : SK_OK;
+}
+
+int sk_dataset_add_palindromes_folded(sk_context* ctx, sk_dataset* ds, int32_t n, const char* const* seqs,
+                                      const char* const* labels, int32_t fold_flags, int32_t seed_length,
+                                      int32_t min_loop, int32_t max_dist, int32_t n_threads) {
+  if (!ctx || !ds || n < 0 || (n > 0 && !seqs)) return fail(ctx, SK_ERR_INVALID, "null argument");
+  if (ds->uploaded) return fail(ctx, SK_ERR_INVALID, "dataset already uploaded");
+  if (ds_mixes(ds, kSortPal)) return fail(ctx, SK_ERR_INVALID, ds->err);
+  // the lowercased sequences (load_examples, simpal/simpal.cpp:298), folded as they are
+  std::vector<std::string> low((size_t)n);
+  std::vector<const char*> lptr((size_t)n);
+  std::vector<size_t> off((size_t)n + 1, 0);
+  for (int32_t i = 0; i < n; ++i) {
+    if (!seqs[i]) return fail(ctx, SK_ERR_INVALID, "null sequence");
+    low[(size_t)i] = lower(seqs[i]);
+    lptr[(size_t)i] = low[(size_t)i].c_str();
+    const size_t m = low[(size_t)i].size();
+    const int rc = pal_args(m, seed_length, min_loop, max_dist, &ds->err);
+    if (rc) return fail(ctx, rc, ds->err);
+    off[(size_t)i + 1] = off[(size_t)i] + (m > 1 ? m * (m - 1) / 2 : 0);
+  }
+  if (pal_seed_differs(ds, seed_length)) return fail(ctx, SK_ERR_INVALID, ds->err);
+  std::vector<double> bpp(std::max<size_t>(off[(size_t)n], 1));
+  int rc = sk_fold_mccaskill(ctx, n, lptr.data(), fold_flags, bpp.data(), nullptr);
+  if (rc) return rc;
+  const size_t base = ds->ex.size();
+  try {
+    ds->ex.resize(base + (size_t)n);
+    for (int32_t i = 0; i < n; ++i) ds->labels.emplace_back(labels && labels[i] ? labels[i] : "+1");
+  } catch (const std::bad_alloc&) {
+    return fail(ctx, SK_ERR_ALLOC, "palindrome examples");
+  }
+  int nt = n_threads > 0 ? n_threads : (int)std::thread::hardware_concurrency();
+  nt = std::max(1, std::min(nt, std::max<int32_t>(n, 1)));
+  std::atomic<int32_t> next(0), status(SK_OK);
+  auto work = [&]() {
+    for (;;) {
+      const int32_t i = next.fetch_add(1);
+      if (i >= n || status.load() != SK_OK) return;
+      try {
+        build_palindromes(ds->ex[base + (size_t)i], low[(size_t)i], bpp.data() + off[(size_t)i], seed_length,
+                          min_loop, max_dist);
+      } catch (...) {
+        status.store(SK_ERR_ALLOC);
+      }
+    }
+  };
+  run_pool(nt, work);
+  if (status.load() != SK_OK) {
+    ds->ex.resize(base);
+    ds->labels.resize(base);
+    return fail(ctx, status.load(), "palindrome example build failed");
+  }
+  return SK_OK;
 }
 
 int sk_random_sequences(uint64_t* state, int32_t n_seqs, int32_t len, char* out) {

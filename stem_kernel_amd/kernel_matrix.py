@@ -31,7 +31,7 @@ __all__ = [
     "fold", "random_sequences", "Dataset", "Context", "KernelMatrix",
     "SuStemKernel", "SiStemKernel", "StringKernel", "SuStemStrKernel", "StemStrKernel",
     "SiStemStrKernel", "LSuStemKernel", "LSuStemStrKernel", "NaiveStringKernel",
-    "StemKernelError", "SVMModel", "LAKernel",
+    "StemKernelError", "SVMModel", "LAKernel", "SimpalKernel", "simpal_shape",
 ]
 
 
@@ -195,6 +195,29 @@ class LAKernel(_Kernel):
         super().__init__(**kw)
 
 
+class SimpalKernel(_Kernel):
+    """KernelFunc(tolerance) of simpal/ (simpal.cpp:225-280), the "Simple
+    Palindrome Kernel", over palindrome datasets (``Dataset.add_palindromes``):
+    the sum over the entries a of x and b of y whose keys differ in at most
+    ``tolerance`` letters of exp(-|d_a - d_b|) w_a w_b.  A negative tolerance
+    counts every key pair (the reference's ``tolerance_ < 0``).  The tolerance
+    travels in the ``mismatch`` field of the parameters."""
+    kind = _lib.SIMPAL
+
+    def __init__(self, tolerance=1):
+        if int(tolerance) != tolerance:
+            raise ValueError("tolerance must be an integer")
+        super().__init__(mismatch=float(int(tolerance)))
+
+
+def simpal_shape():
+    """(y_tile, x_block) of the palindrome kernel (sk_simpal_shape): y entries
+    per LDS tile and x entries per lane; a block of x entries is 64 * x_block."""
+    t, b = C.c_int32(), C.c_int32()
+    check(lib().sk_simpal_shape(C.byref(t), C.byref(b)))
+    return t.value, b.value
+
+
 class StemKernel4D(_Kernel):
     """StemKernel<double,BPMat>(use_GU, loop, gap, stack, subst, band,
     ali_bound, bp_bound) of stem_kernel/ (stem_kernel.h:26-60), full_dp
@@ -328,6 +351,82 @@ class Dataset:
         check(lib().sk_dataset_aa_profile(self._h, i, out.ctypes.data_as(C.POINTER(C.c_float)),
                                           C.byref(ns)))
         return out[:L], ns.value
+
+    def add_palindromes(self, label: str, seq: str, bpp: Optional[np.ndarray] = None, seed_length: int = 3,
+                        min_loop: int = 3, max_dist: int = 300) -> None:
+        """Append one palindrome example: Pals(seq, seed_length, min_loop,
+        max_dist) of simpal/simpal.cpp:37-218 (sk_dataset_add_palindromes;
+        defaults of the CLI, :314-338).  ``bpp``: the packed bp matrix over the
+        characters of ``seq``; ``fold`` of the lowercased sequence without GU
+        pairs when omitted (the synthetic stand-in for PFWrapper(seq, true)).
+        A dataset holds examples of one sort and one seed_length."""
+        if bpp is None:
+            bpp = fold(seq.lower(), no_gu=True)
+        b = np.ascontiguousarray(bpp, dtype=np.float64)
+        m = len(seq)
+        if b.ndim != 1 or b.size != m * (m - 1) // 2:
+            raise ValueError(f"bpp needs {m * (m - 1) // 2} entries, the packed upper triangle over "
+                             f"{m} characters; got {b.size}")
+        if b.size == 0:
+            b = np.zeros(1)
+        check(lib().sk_dataset_add_palindromes(self._h, label.encode(), seq.encode(),
+                                               b.ctypes.data_as(C.POINTER(C.c_double)),
+                                               seed_length, min_loop, max_dist))
+
+    def add_palindromes_folded(self, ctx: "Context", seqs: Sequence[str], labels=None, no_gu: bool = True,
+                               no_closing_gu: bool = False, no_lonely_pairs: bool = False,
+                               seed_length: int = 3, min_loop: int = 3, max_dist: int = 300,
+                               threads: int = 0) -> None:
+        """Append palindrome examples of sequences folded on ctx's GPU
+        (sk_dataset_add_palindromes_folded; sk_fold_mccaskill without GU pairs
+        by default, as PFWrapper(seq, true) of simpal/simpal.cpp:128)."""
+        seqs = list(seqs)
+        n = len(seqs)
+        sarr = (C.c_char_p * max(n, 1))(*[s.encode() for s in seqs])
+        larr = None if labels is None else (C.c_char_p * max(n, 1))(*[l.encode() for l in labels])
+        flags = (1 if no_gu else 0) | (2 if no_closing_gu else 0) | (4 if no_lonely_pairs else 0)
+        ctx._chk(lib().sk_dataset_add_palindromes_folded(ctx.handle, self._h, n, sarr, larr, flags,
+                                                         seed_length, min_loop, max_dist, threads))
+
+    def add_palindrome_entries(self, label: str, keys: Sequence[str], dist, weight,
+                               seed_length: Optional[int] = None) -> None:
+        """Append a palindrome example from explicit entries
+        (sk_dataset_add_palindrome_entries): ``keys`` of seed_length letters of
+        acgu each, ``dist`` >= 0, finite ``weight`` >= 0, no (key, dist) twice.
+        ``seed_length`` is taken from the keys when omitted (needed for an
+        example without entries)."""
+        keys = list(keys)
+        if seed_length is None:
+            if not keys:
+                raise ValueError("seed_length is needed for an example without entries")
+            seed_length = len(keys[0])
+        if any(len(k) != seed_length for k in keys):
+            raise ValueError("every key needs seed_length letters")
+        d = np.ascontiguousarray(dist, dtype=np.int32)
+        w = np.ascontiguousarray(weight, dtype=np.float32)
+        if d.shape != (len(keys),) or w.shape != (len(keys),):
+            raise ValueError("keys, dist and weight need the same length")
+        check(lib().sk_dataset_add_palindrome_entries(
+            self._h, label.encode(), seed_length, len(keys), "".join(keys).encode(),
+            d.ctypes.data_as(C.POINTER(C.c_int32)), w.ctypes.data_as(C.POINTER(C.c_float))))
+
+    def palindromes(self, i: int):
+        """(keys, dist, weight) of palindrome example i in map order (key,
+        then dist): a list of strings, int32 and float32 arrays
+        (sk_dataset_palindromes)."""
+        n = C.c_int32()
+        check(lib().sk_dataset_palindromes(self._h, i, C.byref(n), None, None, None))
+        m = n.value
+        d = np.zeros(max(m, 1), np.int32)
+        w = np.zeros(max(m, 1), np.float32)
+        # a zeroed buffer for the longest keys (32 letters); the library writes
+        # m * seed_length letters, so their count gives seed_length
+        kb = C.create_string_buffer(max(m, 1) * 32)
+        check(lib().sk_dataset_palindromes(self._h, i, None, kb, d.ctypes.data_as(C.POINTER(C.c_int32)),
+                                           w.ctypes.data_as(C.POINTER(C.c_float))))
+        raw = kb.raw.rstrip(b"\0")
+        s = len(raw) // m if m else 0
+        return [raw[k * s:(k + 1) * s].decode() for k in range(m)], d[:m], w[:m]
 
     def add_file(self, label: str, path: str, fmt: str = "fa", th: float = 0.01,
                  use_bp: bool = True, protein: bool = False) -> int:
