@@ -542,6 +542,97 @@ int sk_svm_predict(const sk_svm_model *m, int32_t cnt, const double *row, int32_
                    double *label, double *values);
 const char *sk_svm_last_error(void);
 
+/* ---------------------------------------------------------------- SVM training
+ * Batched two-class C-SVC training on a precomputed Gram: libsvm's SMO solver,
+ * Solver::Solve (libsvm/solver.cpp:81-349) with select_working_set
+ * (:352-451) and calculate_rho (:554-592), called as solve_c_svc does
+ * (libsvm/svm.cpp:38-71) and as the optimizer's svm_train does
+ * (optimizer/gradient.cpp:208-246): p = -1, alpha = 0, G = -1, y = +1 for a
+ * label > 0 and -1 otherwise, bounds Cp (y = +1) and Cn.  What replaces
+ * `svm-train -t 4` on the printed matrix and the per-fold Solve of
+ * GradientComputation::compute (optimizer/gradient.cpp:107-156).  Many
+ * (training subset, C) problems over one Gram are solved in one call: on the
+ * GPU one workgroup per problem (csrc/kernels/svm_smo.hip), on the host one
+ * thread per problem (csrc/host/svm_train.cpp).
+ *
+ * WITHOUT SHRINKING.  The active set is always the whole problem and no index
+ * is swapped, so the sequence of working pairs is a function of the inputs and
+ * both paths give the alphas of the reference's Solve(..., shrinking = 0) bit
+ * for bit.  `svm-train` defaults to -h 1 and gradient.cpp hardcodes
+ * shrinking = 1 (:224): such a run ends within the same stopping tolerance
+ * but not at the same bits (on a 1,040-example Gram with C = 10, eps = 1e-3:
+ * obj differs by 2e-8 relative, rho by 2e-4).
+ *
+ * Arithmetic kept from the reference:
+ *   Q_i[k] = (float)(y_i y_k K[t_i][t_k]), QD[k] = (float)K[t_k][t_k]
+ *   (SVC_Q, libsvm/qmatrix.cpp:339-362; kernel_precomputed :331-336), t the
+ *   problem's training list, K read by row only (row t_i for Q_i);
+ *   working-set selection with >= and <=, so of equal candidates the last
+ *   index wins (solver.cpp:368-386, :393-443); quad_coef in float arithmetic
+ *   (:405, :429, :182, :225), TAU = 1e-12 when it is <= 0; the clipped
+ *   two-variable update (:180-265); G[k] += Q_i[k]*da_i + Q_j[k]*da_j with
+ *   four roundings and no fused multiply-add (:272-275); stop when
+ *   Gmax + Gmax2 < eps (:445); rho and obj as :554-592 and :314-321.
+ * One addition: max_iter, a mandatory cap on the iterations (the reference's
+ * loop has none).  A problem that needs a further iteration after max_iter
+ * returns its state at that point with status SK_SVM_NOT_CONVERGED; that is
+ * not an error of the call.
+ *
+ * Decision values of a problem's test list: sum over a of (alpha_a y_a) *
+ * K[s][t_a] - rho (svm_predict, optimizer/gradient.cpp:248-278); the host
+ * path sums in training order over alpha_a != 0, the GPU sums in parallel. */
+typedef struct {
+  const int32_t *train; /* indices into the Gram, in training order */
+  int32_t n_train;
+  const int32_t *test;  /* examples to evaluate after the solve (may be NULL) */
+  int32_t n_test;
+  double Cp, Cn, eps;
+  int64_t max_iter;
+} sk_svm_problem;
+typedef enum {
+  SK_SVM_CONVERGED = 0,
+  SK_SVM_NOT_CONVERGED = 1, /* max_iter reached */
+  SK_SVM_NO_PAIR = 2        /* no working pair (a Gram that is not finite) */
+} sk_svm_status;
+typedef struct {
+  double rho, obj;
+  int64_t iterations;
+  int32_t status;  /* sk_svm_status */
+  int32_t n_free;  /* 0 < alpha < C */
+  int32_t n_bound; /* alpha at its upper bound */
+} sk_svm_solution;
+/* gram: n x n row-major host memory as sk_gram writes it, uploaded once per
+ * call; labels: n values.  alpha_out (sum of n_train; alpha >= 0, not
+ * multiplied by y) and dec_out (sum of n_test; may be NULL when that is 0)
+ * are concatenated in problem order; solutions has n_problems entries.
+ * SK_ERR_INVALID, with nothing launched, for an index outside [0, n), a
+ * training list with one class only (the reference's rho would be infinite),
+ * eps <= 0, Cp <= 0 or Cn <= 0, max_iter < 1 or n_train < 2;
+ * SK_ERR_UNSUPPORTED, with nothing launched, for a training list longer than
+ * sk_svm_train_shape's largest.  The kernel launches are counted by
+ * sk_last_launch_ms (one per size class in use). */
+int sk_svm_train_batch(sk_context *ctx, const double *gram, int32_t n, const double *labels,
+                       const sk_svm_problem *problems, int32_t n_problems, double *alpha_out,
+                       double *dec_out, sk_svm_solution *solutions);
+/* The same on n_threads host threads (0 = hardware concurrency), any n_train. */
+int sk_svm_train_batch_host(const double *gram, int32_t n, const double *labels,
+                            const sk_svm_problem *problems, int32_t n_problems, int32_t n_threads,
+                            double *alpha_out, double *dec_out, sk_svm_solution *solutions);
+/* Size classes of the GPU solver: class c takes n_train <= bounds[c]
+ * (ascending; up to 4 written), *n_classes of them, *max_train the last. */
+int sk_svm_train_shape(int32_t *bounds, int32_t *n_classes, int32_t *max_train);
+/* A two-class C-SVC precomputed-kernel model in svm_save_model's text format
+ * (libsvm/svm.cpp:1201-1286: rho %g, coefficients %.16g, support vectors
+ * 0:serial with the 1-based serial number train[a] + 1), which
+ * sk_svm_model_load reads back.  Classes in svm_group_classes' order
+ * (svm.cpp:611-666: by first appearance in the training list, label (int));
+ * libsvm's first class is its +1, so when the first training label is not
+ * > 0 the coefficients and rho change sign.  Support vectors are the
+ * alpha != 0 examples, the first class's before the second's.  SK_ERR_INVALID
+ * unless the training labels have exactly two (int) values, one > 0. */
+int sk_svm_model_write(const char *path, const double *labels, int32_t n, const int32_t *train,
+                       int32_t n_train, const double *alpha, double rho);
+
 /* ---------------------------------------------------------------- diagnostics */
 /* Milliseconds spent in the last compute call's dominant kernel (DAG stem
  * DP), measured with HIP events on the context's stream, and its launch

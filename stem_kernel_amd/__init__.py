@@ -8,5 +8,9 @@ from .kernel_matrix import (  # noqa: F401
     SiStemStrKernel, SimpalKernel, StemKernel4D, StemStrKernel, StringKernel, SuStemKernel, SuStemStrKernel, fold,
     format_libsvm, parse_examples, random_sequences, read_examples, simpal_shape,
 )
+from .svm import (  # noqa: F401
+    DEFAULT_MAX_ITER, CrossValidation, SVMSolution, cross_validate, cv_split, svm_train, svm_train_batch,
+    svm_train_shape,
+)
 
 __version__ = "0.1.0"

@@ -42,6 +42,17 @@ class KernelParams(C.Structure):
     ]
 
 
+class SvmProblem(C.Structure):  # sk_svm_problem
+    _fields_ = [("train", C.POINTER(C.c_int32)), ("n_train", C.c_int32), ("test", C.POINTER(C.c_int32)),
+                ("n_test", C.c_int32), ("Cp", C.c_double), ("Cn", C.c_double), ("eps", C.c_double),
+                ("max_iter", C.c_int64)]
+
+
+class SvmSolution(C.Structure):  # sk_svm_solution
+    _fields_ = [("rho", C.c_double), ("obj", C.c_double), ("iterations", C.c_int64), ("status", C.c_int32),
+                ("n_free", C.c_int32), ("n_bound", C.c_int32)]
+
+
 _P = C.c_void_p
 _I32P = C.POINTER(C.c_int32)
 _U32P = C.POINTER(C.c_uint32)
@@ -153,6 +164,12 @@ SIGNATURES = {
     "sk_svm_predict": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_double), C.c_int32, C.c_int32,
                                  C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "sk_svm_last_error": (C.c_char_p, []),
+    "sk_svm_train_batch": (C.c_int, [_P, _F64P, C.c_int32, _F64P, C.POINTER(SvmProblem), C.c_int32, _F64P, _F64P,
+                                     C.POINTER(SvmSolution)]),
+    "sk_svm_train_batch_host": (C.c_int, [_F64P, C.c_int32, _F64P, C.POINTER(SvmProblem), C.c_int32, C.c_int32,
+                                          _F64P, _F64P, C.POINTER(SvmSolution)]),
+    "sk_svm_train_shape": (C.c_int, [_I32P, _I32P, _I32P]),
+    "sk_svm_model_write": (C.c_int, [C.c_char_p, _F64P, C.c_int32, _I32P, C.c_int32, _F64P, C.c_double]),
 }
 
 _lock = threading.Lock()

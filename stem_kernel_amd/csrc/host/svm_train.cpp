@@ -1,0 +1,391 @@
+// Portions (the SMO iteration below keeps libsvm's operation order, and so its
+// structure, for bit-compatible alphas) derive from LIBSVM:
+//   Copyright (c) 2000-2007 Chih-Chung Chang and Chih-Jen Lin.
+//   All rights reserved.
+//   Redistribution and use in source and binary forms, with or without
+//   modification, are permitted provided that the following conditions are
+//   met: 1. Redistributions of source code must retain the above copyright
+//   notice, this list of conditions and the following disclaimer.
+//   2. Redistributions in binary form must reproduce the above copyright
+//   notice, this list of conditions and the following disclaimer in the
+//   documentation and/or other materials provided with the distribution.
+//   3. Neither name of copyright holders nor the names of its contributors
+//   may be used to endorse or promote products derived from this software
+//   without specific prior written permission.
+//   THIS SOFTWARE IS PROVIDED BY THE COPYRIGHT HOLDERS AND CONTRIBUTORS "AS
+//   IS" AND ANY EXPRESS OR IMPLIED WARRANTIES, INCLUDING, BUT NOT LIMITED TO,
+//   THE IMPLIED WARRANTIES OF MERCHANTABILITY AND FITNESS FOR A PARTICULAR
+//   PURPOSE ARE DISCLAIMED.  IN NO EVENT SHALL THE REGENTS OR CONTRIBUTORS BE
+//   LIABLE FOR ANY DIRECT, INDIRECT, INCIDENTAL, SPECIAL, EXEMPLARY, OR
+//   CONSEQUENTIAL DAMAGES (INCLUDING, BUT NOT LIMITED TO, PROCUREMENT OF
+//   SUBSTITUTE GOODS OR SERVICES; LOSS OF USE, DATA, OR PROFITS; OR BUSINESS
+//   INTERRUPTION) HOWEVER CAUSED AND ON ANY THEORY OF LIABILITY, WHETHER IN
+//   CONTRACT, STRICT LIABILITY, OR TORT (INCLUDING NEGLIGENCE OR OTHERWISE)
+//   ARISING IN ANY WAY OUT OF THE USE OF THIS SOFTWARE, EVEN IF ADVISED OF
+//   THE POSSIBILITY OF SUCH DAMAGE.
+//
+// Two-class C-SVC training on a precomputed Gram: the reference's SMO solver
+// without shrinking, restated from the published algorithm (Fan, Chen and
+// Lin, JMLR 6 (2005), working-set selection 3):
+//   Solver::Solve            libsvm/solver.cpp:81-349   (start :113-135, the
+//                            two-variable update :180-265, G update :272-275,
+//                            obj :314-321)
+//   select_working_set       solver.cpp:352-451
+//   calculate_rho            solver.cpp:554-592
+//   update_alpha_status      libsvm/solver.h:67-74
+//   SVC_Q                    libsvm/qmatrix.cpp:339-362 (QD, get_Q: float)
+//   kernel_precomputed       qmatrix.cpp:331-336
+//   solve_c_svc              libsvm/svm.cpp:38-71       (p = -1, alpha = 0, y)
+//   svm_train / svm_predict  optimizer/gradient.cpp:208-246, :248-278
+//   svm_save_model           svm.cpp:1201-1286, svm_group_classes :611-666
+// With the active set whole, reconstruct_gradient and the second selection
+// change nothing (solver.cpp:154-165), G_bar is never read, and the Q cache
+// (a store of rows, qmatrix.cpp:37-60) does not touch a value.
+//
+// This file is the CPU path of sk_svm_train_batch, what tests/golden/
+// svm_train.json pins, and what the GPU kernel (kernels/svm_smo.hip) is
+// compared with.  Built with -ffp-contract=off: the G update has four
+// roundings.
+#include "svm_train.h"
+
+#include <algorithm>
+#include <atomic>
+#include <cmath>
+#include <cstdio>
+#include <limits>
+#include <system_error>
+#include <thread>
+#include <vector>
+
+namespace {
+
+constexpr double kTau = 1e-12;
+constexpr double kInf = std::numeric_limits<double>::infinity();
+enum : char { kLower, kUpper, kFree };
+
+struct Smo {
+  const double* K;
+  size_t n;
+  const int32_t* t;
+  int l;
+  double Cp, Cn;
+  std::vector<signed char> y;
+  std::vector<float> QD, Qi, Qj;
+  std::vector<double> G;
+  std::vector<char> st;
+  double* alpha;
+
+  double bound(int k) const { return y[k] > 0 ? Cp : Cn; }
+  void status(int k) { st[k] = alpha[k] >= bound(k) ? kUpper : alpha[k] <= 0 ? kLower : kFree; }
+  // row i of Q: the int product of the labels times the double, rounded to float
+  void row(int i, std::vector<float>& q) const {
+    const double* r = K + (size_t)t[i] * n;
+    const int yi = y[i];
+    for (int k = 0; k < l; ++k) q[k] = (float)(yi * y[k] * r[t[k]]);
+  }
+};
+
+void solve_one(const double* K, int32_t n, const double* labels, const sk_svm_problem& P, double* alpha,
+               double* dec, sk_svm_solution& S) {
+  Smo s;
+  s.K = K;
+  s.n = (size_t)n;
+  s.t = P.train;
+  const int l = s.l = P.n_train;
+  s.Cp = P.Cp;
+  s.Cn = P.Cn;
+  s.alpha = alpha;
+  s.y.resize(l);
+  s.QD.resize(l);
+  s.Qi.resize(l);
+  s.Qj.resize(l);
+  s.G.assign(l, -1.0);
+  s.st.assign(l, kLower);
+  for (int k = 0; k < l; ++k) {
+    s.y[k] = labels[s.t[k]] > 0 ? +1 : -1;
+    s.QD[k] = (float)K[(size_t)s.t[k] * s.n + s.t[k]];
+    alpha[k] = 0.0;
+  }
+  const std::vector<signed char>& y = s.y;
+  std::vector<double>& G = s.G;
+  const std::vector<float>&QD = s.QD, &Qi = s.Qi, &Qj = s.Qj;
+
+  int64_t iter = 0;
+  int32_t status = SK_SVM_CONVERGED;
+  for (;;) {
+    // i: the last maximiser of -y G over I_up
+    double gmax = -kInf, gmax2 = -kInf, od_min = kInf;
+    int i = -1, j = -1;
+    for (int k = 0; k < l; ++k) {
+      if (y[k] > 0) {
+        if (s.st[k] != kUpper && -G[k] >= gmax) gmax = -G[k], i = k;
+      } else {
+        if (s.st[k] != kLower && G[k] >= gmax) gmax = G[k], i = k;
+      }
+    }
+    if (i >= 0) s.row(i, s.Qi);
+    // j: the last minimiser of the objective's decrease over I_low
+    for (int k = 0; k < l; ++k) {
+      double gd;
+      float qf;
+      if (y[k] > 0) {
+        if (s.st[k] == kLower) continue;
+        gd = gmax + G[k];
+        if (G[k] >= gmax2) gmax2 = G[k];
+        if (!(gd > 0)) continue;
+        qf = Qi[i] + QD[k] - 2 * y[i] * Qi[k];  // float arithmetic
+      } else {
+        if (s.st[k] == kUpper) continue;
+        gd = gmax - G[k];
+        if (-G[k] >= gmax2) gmax2 = -G[k];
+        if (!(gd > 0)) continue;
+        qf = Qi[i] + QD[k] + 2 * y[i] * Qi[k];
+      }
+      const double qc = qf;
+      const double od = qc > 0 ? -(gd * gd) / qc : -(gd * gd) / kTau;
+      if (od <= od_min) od_min = od, j = k;
+    }
+    if (gmax + gmax2 < P.eps) break;
+    if (i < 0 || j < 0) {
+      status = SK_SVM_NO_PAIR;
+      break;
+    }
+    if (iter == P.max_iter) {
+      status = SK_SVM_NOT_CONVERGED;
+      break;
+    }
+    ++iter;
+    s.row(j, s.Qj);
+
+    const double Ci = s.bound(i), Cj = s.bound(j);
+    const double ai0 = alpha[i], aj0 = alpha[j];
+    if (y[i] != y[j]) {
+      const float qf = Qi[i] + Qj[j] + 2 * Qi[j];
+      double qc = qf;
+      if (qc <= 0) qc = kTau;
+      const double delta = (-G[i] - G[j]) / qc;
+      const double diff = alpha[i] - alpha[j];
+      alpha[i] += delta;
+      alpha[j] += delta;
+      if (diff > 0) {
+        if (alpha[j] < 0) alpha[j] = 0, alpha[i] = diff;
+      } else {
+        if (alpha[i] < 0) alpha[i] = 0, alpha[j] = -diff;
+      }
+      if (diff > Ci - Cj) {
+        if (alpha[i] > Ci) alpha[i] = Ci, alpha[j] = Ci - diff;
+      } else {
+        if (alpha[j] > Cj) alpha[j] = Cj, alpha[i] = Cj + diff;
+      }
+    } else {
+      const float qf = Qi[i] + Qj[j] - 2 * Qi[j];
+      double qc = qf;
+      if (qc <= 0) qc = kTau;
+      const double delta = (G[i] - G[j]) / qc;
+      const double sum = alpha[i] + alpha[j];
+      alpha[i] -= delta;
+      alpha[j] += delta;
+      if (sum > Ci) {
+        if (alpha[i] > Ci) alpha[i] = Ci, alpha[j] = sum - Ci;
+      } else {
+        if (alpha[j] < 0) alpha[j] = 0, alpha[i] = sum;
+      }
+      if (sum > Cj) {
+        if (alpha[j] > Cj) alpha[j] = Cj, alpha[i] = sum - Cj;
+      } else {
+        if (alpha[i] < 0) alpha[i] = 0, alpha[j] = sum;
+      }
+    }
+    const double dai = alpha[i] - ai0, daj = alpha[j] - aj0;
+    for (int k = 0; k < l; ++k) G[k] += Qi[k] * dai + Qj[k] * daj;
+    s.status(i);
+    s.status(j);
+  }
+
+  // rho: the mean of y G over the free variables, else the bounds' midpoint
+  int n_free = 0, n_bound = 0;
+  double ub = kInf, lb = -kInf, sum_free = 0;
+  for (int k = 0; k < l; ++k) {
+    const double yg = y[k] * G[k];
+    if (s.st[k] == kUpper) {
+      ++n_bound;
+      if (y[k] < 0) ub = std::min(ub, yg);
+      else lb = std::max(lb, yg);
+    } else if (s.st[k] == kLower) {
+      if (y[k] > 0) ub = std::min(ub, yg);
+      else lb = std::max(lb, yg);
+    } else {
+      ++n_free;
+      sum_free += yg;
+    }
+  }
+  S.rho = n_free > 0 ? sum_free / n_free : (ub + lb) / 2;
+  double v = 0;
+  for (int k = 0; k < l; ++k) v += alpha[k] * (G[k] + -1.0);
+  S.obj = v / 2;
+  S.iterations = iter;
+  S.status = status;
+  S.n_free = n_free;
+  S.n_bound = n_bound;
+
+  for (int q = 0; q < P.n_test; ++q) {
+    const double* r = K + (size_t)P.test[q] * s.n;
+    double sum = 0.0;
+    for (int a = 0; a < l; ++a)
+      if (alpha[a] != 0.0) sum += alpha[a] * y[a] * r[s.t[a]];
+    dec[q] = sum - S.rho;
+  }
+}
+
+}  // namespace
+
+namespace sk {
+
+int svm_check_batch(const double* gram, int32_t n, const double* labels, const sk_svm_problem* problems,
+                    int32_t n_problems, const double* alpha_out, const double* dec_out,
+                    const sk_svm_solution* solutions, int32_t max_train, int64_t* sum_train,
+                    int64_t* sum_test, std::string& err) {
+  auto bad = [&](int p, const char* what) {
+    err = "sk_svm_train_batch: problem " + std::to_string(p) + ": " + what;
+    return (int)SK_ERR_INVALID;
+  };
+  if (!gram || !labels || n < 1 || n_problems < 0 || (n_problems && !problems) || !alpha_out ||
+      (n_problems && !solutions)) {
+    err = "sk_svm_train_batch: null or empty argument";
+    return SK_ERR_INVALID;
+  }
+  int64_t st = 0, ss = 0;
+  for (int p = 0; p < n_problems; ++p) {
+    const sk_svm_problem& P = problems[p];
+    if (P.n_train < 2 || !P.train) return bad(p, "n_train < 2");
+    if (P.n_test < 0 || (P.n_test && !P.test)) return bad(p, "test list");
+    if (!(P.eps > 0)) return bad(p, "eps <= 0");
+    if (!(P.Cp > 0) || !(P.Cn > 0)) return bad(p, "C <= 0");
+    if (P.max_iter < 1) return bad(p, "max_iter < 1");
+    bool pos = false, neg = false;
+    for (int k = 0; k < P.n_train; ++k) {
+      const int32_t t = P.train[k];
+      if (t < 0 || t >= n) return bad(p, "training index outside [0, n)");
+      (labels[t] > 0 ? pos : neg) = true;
+    }
+    for (int k = 0; k < P.n_test; ++k)
+      if (P.test[k] < 0 || P.test[k] >= n) return bad(p, "test index outside [0, n)");
+    if (!pos || !neg) return bad(p, "training list with one class only");
+    st += P.n_train;
+    ss += P.n_test;
+  }
+  if (ss && !dec_out) {
+    err = "sk_svm_train_batch: dec_out is null";
+    return SK_ERR_INVALID;
+  }
+  if (max_train > 0)
+    for (int p = 0; p < n_problems; ++p)
+      if (problems[p].n_train > max_train) {
+        err = "sk_svm_train_batch: problem " + std::to_string(p) + ": n_train " +
+              std::to_string(problems[p].n_train) + " over the GPU solver's " + std::to_string(max_train);
+        return SK_ERR_UNSUPPORTED;
+      }
+  *sum_train = st;
+  *sum_test = ss;
+  return SK_OK;
+}
+
+}  // namespace sk
+
+extern "C" {
+
+int sk_svm_train_batch_host(const double* gram, int32_t n, const double* labels, const sk_svm_problem* problems,
+                            int32_t n_problems, int32_t n_threads, double* alpha_out, double* dec_out,
+                            sk_svm_solution* solutions) {
+  try {
+    std::string err;
+    int64_t st = 0, ss = 0;
+    const int rc = sk::svm_check_batch(gram, n, labels, problems, n_problems, alpha_out, dec_out, solutions, 0,
+                                       &st, &ss, err);
+    if (rc) return rc;
+    if (n_threads < 0) return SK_ERR_INVALID;
+    std::vector<int64_t> aoff(n_problems + 1, 0), doff(n_problems + 1, 0);
+    for (int p = 0; p < n_problems; ++p) {
+      aoff[p + 1] = aoff[p] + problems[p].n_train;
+      doff[p + 1] = doff[p] + problems[p].n_test;
+    }
+    int nt = n_threads ? n_threads : (int)std::max(1u, std::thread::hardware_concurrency());
+    nt = std::max(1, std::min(nt, n_problems));
+    std::atomic<int> cursor{0};
+    std::atomic<bool> oom{false};
+    auto work = [&] {
+      for (int p; (p = cursor.fetch_add(1)) < n_problems;) {
+        try {
+          solve_one(gram, n, labels, problems[p], alpha_out + aoff[p], dec_out ? dec_out + doff[p] : nullptr,
+                    solutions[p]);
+        } catch (const std::bad_alloc&) {
+          oom = true;
+        }
+      }
+    };
+    std::vector<std::thread> th;
+    for (int t = 1; t < nt; ++t) {
+      try {
+        th.emplace_back(work);
+      } catch (const std::system_error&) {
+        break;  // the calling thread's share drains the cursor
+      }
+    }
+    work();
+    for (auto& x : th) x.join();
+    return oom ? SK_ERR_ALLOC : SK_OK;
+  } catch (const std::bad_alloc&) {
+    return SK_ERR_ALLOC;
+  }
+}
+
+int sk_svm_train_shape(int32_t* bounds, int32_t* n_classes, int32_t* max_train) {
+  if (bounds)
+    for (int c = 0; c < sk::kSvmClasses; ++c) bounds[c] = sk::kSvmThreads[c] * sk::kSvmElems;
+  if (n_classes) *n_classes = sk::kSvmClasses;
+  if (max_train) *max_train = sk::kSvmMaxTrain;
+  return SK_OK;
+}
+
+int sk_svm_model_write(const char* path, const double* labels, int32_t n, const int32_t* train, int32_t n_train,
+                       const double* alpha, double rho) {
+  if (!path || !labels || !train || !alpha || n_train < 2) return SK_ERR_INVALID;
+  // svm_group_classes: classes by first appearance of the (int) label
+  int lab[2] = {0, 0}, ncls = 0;
+  bool pos[2] = {false, false};
+  std::vector<signed char> cls(n_train);
+  for (int k = 0; k < n_train; ++k) {
+    if (train[k] < 0 || train[k] >= n) return SK_ERR_INVALID;
+    const double v = labels[train[k]];
+    if (!(std::fabs(v) < 2147483648.0)) return SK_ERR_INVALID;
+    const int il = (int)v;
+    int c = 0;
+    while (c < ncls && lab[c] != il) ++c;
+    if (c == ncls) {
+      if (ncls == 2) return SK_ERR_INVALID;
+      lab[ncls] = il;
+      pos[ncls++] = v > 0;
+    } else if (pos[c] != (v > 0)) {
+      return SK_ERR_INVALID;  // one (int) label on both sides of the solver's y
+    }
+    cls[k] = (signed char)c;
+  }
+  if (ncls != 2 || pos[0] == pos[1]) return SK_ERR_INVALID;
+  // libsvm's +1 is its first class: the solver's y = +1 is label > 0
+  const double sgn = pos[0] ? 1.0 : -1.0;
+  int nsv[2] = {0, 0};
+  for (int k = 0; k < n_train; ++k)
+    if (alpha[k] != 0.0) ++nsv[cls[k]];
+  FILE* f = std::fopen(path, "w");
+  if (!f) return SK_ERR_INVALID;
+  std::fprintf(f, "svm_type c_svc\nkernel_type precomputed\nnr_class 2\ntotal_sv %d\n", nsv[0] + nsv[1]);
+  std::fprintf(f, "rho %g\nlabel %d %d\nnr_sv %d %d\nSV\n", sgn * rho, lab[0], lab[1], nsv[0], nsv[1]);
+  for (int c = 0; c < 2; ++c)
+    for (int k = 0; k < n_train; ++k)
+      if (cls[k] == c && alpha[k] != 0.0)
+        std::fprintf(f, "%.16g 0:%d \n", sgn * (alpha[k] * (pos[c] ? 1 : -1)), train[k] + 1);
+  const bool bad = std::ferror(f) != 0;
+  return (std::fclose(f) != 0 || bad) ? SK_ERR_INVALID : SK_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,105 @@
+#!/usr/bin/env python3
+"""Batched C-SVC training (sk_svm_train_batch, csrc/kernels/svm_smo.hip) on
+one MI355X against the host path on 16 threads.
+
+Workload: model selection over one 2,048-example Gram -- 5 folds (the
+reference's split) x 10 values of C (2^-6 .. 2^3), eps 1e-3: 50 problems of
+1,638 or 1,639 training examples, each with its fold's test list.  The Gram
+is an integer Gram (tests/svm_ref.py: rank 16, random labels, so every
+problem is hard for its C and the iteration counts spread over two orders of
+magnitude).
+
+Timed, each the median of --calls calls after --warmup warm-ups:
+  gpu batch      the 50 problems in one call: wall time of the call (upload
+                 of the 32 MB Gram, kernels, download) and the GPU span of its
+                 kernel launches (HIP events, Context.last_launch_ms)
+  host batch     sk_svm_train_batch_host on --threads threads, same problems
+and once: every problem in a call of its own on the GPU (kernel time of one
+workgroup alone: iterations/s per workgroup, and what the batch gains over
+running them one after another).  Iterations/s per card is the batch's total
+iterations over its GPU span.  The alphas of the two paths are compared bit
+for bit.  Writes one JSON document (--out).  For scale, the reference
+Solver's single-core time on one of these problems is what
+tools/make_golden_svm_train.py prints (DESIGN.md records it)."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import stem_kernel_amd as ska  # noqa: E402
+from tests import svm_ref  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--n", type=int, default=2048)
+    ap.add_argument("--folds", type=int, default=5)
+    ap.add_argument("--calls", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--threads", type=int, default=16)
+    ap.add_argument("--max-iter", type=int, default=2_000_000)
+    ap.add_argument("--out", default="")
+    a = ap.parse_args()
+    K, y = svm_ref.int_gram(0x5A17B001, a.n, 16, 4)
+    Cs = [2.0 ** e for e in range(-6, 4)]
+    folds = [svm_ref.split(a.n, a.folds, f) for f in range(a.folds)]
+    ps = [dict(train=tr, test=ts, C=c, eps=1e-3, max_iter=a.max_iter) for c in Cs for tr, ts in folds]
+    ctx = ska.Context(0)
+
+    wall, span = [], []
+    for it in range(a.warmup + a.calls):
+        t0 = time.perf_counter()
+        gpu = ska.svm_train_batch(K, y, ps, ctx=ctx)
+        t1 = time.perf_counter()
+        if it >= a.warmup:
+            wall.append((t1 - t0) * 1e3)
+            span.append(ctx.last_launch_ms()["ms_sum"])
+    hwall = []
+    for it in range(1 + a.calls):
+        t0 = time.perf_counter()
+        host = ska.svm_train_batch(K, y, ps, n_threads=a.threads)
+        t1 = time.perf_counter()
+        if it >= 1:
+            hwall.append((t1 - t0) * 1e3)
+    same = all(np.array_equal(g.alpha.view(np.int64), h.alpha.view(np.int64)) and g.iterations == h.iterations
+               for g, h in zip(gpu, host))
+    iters = [s.iterations for s in gpu]
+    solo_ms = []
+    for p in ps:  # one workgroup alone on the card
+        ska.svm_train_batch(K, y, [p], ctx=ctx)
+        solo_ms.append(ctx.last_launch_ms()["ms_sum"])
+    rate = [i / (ms * 1e-3) for i, ms in zip(iters, solo_ms)]
+    mspan, mwall, mhost = statistics.median(span), statistics.median(wall), statistics.median(hwall)
+    res = dict(
+        device="MI355X (gfx950)", n=a.n, folds=a.folds, Cs=Cs, problems=len(ps), eps=1e-3,
+        n_train=sorted({len(p["train"]) for p in ps}), shape=ska.svm_train_shape(),
+        calls=a.calls, warmup=a.warmup, host_threads=a.threads,
+        iterations=iters, total_iterations=int(sum(iters)), all_converged=all(s.converged for s in gpu),
+        alphas_bit_equal_gpu_host=bool(same),
+        gpu_batch_wall_ms=wall, gpu_batch_span_ms=span, host_batch_wall_ms=hwall,
+        median_gpu_batch_wall_ms=mwall, median_gpu_batch_span_ms=mspan, median_host_batch_wall_ms=mhost,
+        host_over_gpu_span=mhost / mspan, host_over_gpu_wall=mhost / mwall,
+        solo_kernel_ms=solo_ms, solo_kernel_ms_sum=float(sum(solo_ms)),
+        batch_gain_over_one_after_another=float(sum(solo_ms)) / mspan,
+        iterations_per_s_per_workgroup=dict(min=min(rate), median=statistics.median(rate), max=max(rate)),
+        us_per_iteration_one_workgroup=1e6 / statistics.median(rate),
+        iterations_per_s_per_card=sum(iters) / (mspan * 1e-3),
+        row_cache="not built: no LDS cache of Q rows in this kernel, so no hit rate",
+        accuracy=ska.CrossValidation(Cs, folds, [gpu[k * a.folds:(k + 1) * a.folds] for k in range(len(Cs))],
+                                     y).accuracy,
+    )
+    text = json.dumps(res, indent=1)
+    print(text)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(text + "\n")
+
+
+if __name__ == "__main__":
+    main()
