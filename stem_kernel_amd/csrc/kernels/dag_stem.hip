@@ -1143,11 +1143,107 @@ __device__ __forceinline__ void gamma_rows(const StemLaunch& P, const YView& Y, 
   }
 }
 
-// The Gamma tables of a launch (P.gam_shared): workgroup b stages the y of
-// slot b as the stem kernel does and writes its table P.gam + b gam_doubles
-// and sums P.kap_y + b n_gam.  Runs ahead of sk_dag_stem_kernel, which is
-// ordered behind it: the kernel boundary makes the tables visible to every
-// workgroup.
+// Phi rows of the staged y (gapless y only) from its Gamma table gamtab, for
+// the phi keys t = (code a, len, gamma key g) keys[pb .. pe) (keys = nullptr:
+// the keys pb .. pe - 1 themselves):
+// M_t[q] = co[a][bp(q)] p(q) sum_{cy in ch(q)} g^gy Gamma_g[cy] over
+// the y stems q in len's band; Phi_t = its IY sweep, into row t of phitab;
+// kappa_t = sum_q M_t[q] P_y[q], into phikap[t] (a phi row's MATCH row is
+// pf_p sum_c w_c M_{t(c)} plus its Gamma_{a,len} part).
+// The keys come sorted by gamma key: wave w takes the w-th contiguous share,
+// and H_g[q] = sum_{cy in ch(q)} g^gy Gamma_g[cy] (independent of the key's
+// code and length) is formed once per gamma key from the Gamma row staged in
+// the wave's LDS row R.  A key's row and sum depend on nothing but the key
+// and the y, so whichever keys a wave takes, the stem kernel's per-workgroup
+// tables and the table kernel's shared ones hold the same bits.  The caller
+// orders the Gamma table ahead (a barrier) and the readers behind.
+template <int MAXK>
+__device__ __forceinline__ void phi_rows(const StemLaunch& P, const YView& Y, lds_f64* R, const lds_f64* co,
+                                         const lds_f64* gp, const double* gamtab, double* phitab,
+                                         double* phikap, const int32_t* __restrict__ keys, int pb, int pe,
+                                         int wave_u, int nwaves, int lane) {
+  const DevSet& s = P.yset;
+  const DevSet& xset = P.xset;
+  const int band = (int)P.band;
+  const int nb = Y.nb, bb = Y.bb;
+  const int share = (pe - pb + nwaves - 1) / nwaves;
+  const int t0 = pb + wave_u * share, t1 = min(pe, t0 + share);
+  int gcur = -1;
+  double Hr[MAXK];
+#pragma unroll
+  for (int k = 0; k < MAXK; ++k) Hr[k] = 0.0;
+  for (int t = t0; t < t1; ++t) {
+    const int idx = keys ? __builtin_amdgcn_readfirstlane(keys[t]) : t;
+    const int g = __builtin_amdgcn_readfirstlane((int)xset.phi_g[idx]);
+    if (g != gcur) {
+      gcur = g;
+      const double* __restrict__ grow = gamtab + (size_t)g * (64 * MAXK);
+#pragma unroll
+      for (int k = 0; k < MAXK; ++k) R[lane + 64 * k] = grow[lane + 64 * k];
+      wave_sync();
+      for (int k = 0; k < MAXK; ++k) {
+        const int q = lane + 64 * k;
+        double H = 0.0;
+        if (q < Y.nl) {
+          const uint32_t na = Y.nrg[q].x;
+          const int ne = (int)((na >> 16) & 0xff), e0 = (int)(na & 0xffff);
+          for (int e = 0; e < ne; ++e) {
+            const uint32_t rec = edges_global<MAXK>() ? Y.ed2g[e0 + e] : Y.ed2[e0 + e];
+            H += gp[rec >> 22] * R[rec & 0x7ff];
+          }
+        }
+        Hr[k] = H;
+      }
+      wave_sync();
+    }
+    const uint32_t al = xset.phi_al[idx];
+    const int acode = (int)(al >> 16) * 16, alen = (int)(al & 0xffff);
+    double kp = 0.0;
+#pragma unroll
+    for (int k = 0; k < MAXK; ++k) {
+      const int q = lane + 64 * k;
+      double M = 0.0;
+      if (q < Y.nl) {
+        const uint4 nd = Y.nrg[q];
+        const int ylen = (int)(s.yn_b[nb + q] & 0xffff);
+        if (Hr[k] != 0.0 && (band == 0 || abs(alen - ylen) <= band)) {
+          double vs;
+          if ((nd.y >> 24) != 0u) {
+            vs = co[acode + ((nd.y >> 16) & 0xf)] * (double)__uint_as_float(nd.w);
+          } else {
+            vs = 0.0;
+            const int yb0 = (int)(s.yn_b[nb + q] >> 16), ynb = (int)(nd.x >> 24);
+            for (int b = 0; b < ynb; ++b)
+              vs += co[acode + s.bpf_code[bb + yb0 + b]] * (double)s.bpf_p[bb + yb0 + b];
+          }
+          M = vs * Hr[k];
+          kp += M * s.yn_P[nb + q];
+        }
+      }
+      R[q] = M;
+    }
+    for (int off = 32; off > 0; off >>= 1) kp += __shfl_xor(kp, off, 64);
+    if (lane == 0) phikap[idx] = kp;
+    wave_sync();
+    int c0 = 0;
+    if (band > 0) c0 = Y.ycs[min(max(alen - band, 0), Y.lmax + 1)];
+    c0 = __builtin_amdgcn_readfirstlane(c0);
+    if (c0 < Y.nch) iy_sweep<node_weights<MAXK>(), node_weights_f32<MAXK>()>(Y, R, c0, lane);
+    double* prow = phitab + (size_t)idx * (64 * MAXK);
+#pragma unroll
+    for (int k = 0; k < MAXK; ++k)
+      if (lane + 64 * k < Y.nl) prow[lane + 64 * k] = R[lane + 64 * k];
+    wave_sync();
+  }
+}
+
+// The Gamma and Phi tables of a launch (P.gam_shared, P.phi_shared):
+// workgroup b stages the y of slot b as the stem kernel does and writes its
+// Gamma table P.gam + b gam_doubles and sums P.kap_y + b n_gam, then (behind
+// a barrier: the Phi rows read the Gamma rows of every wave) its Phi table
+// and sums P.phi + b phi_doubles, every phi key of the x set.  Runs ahead of
+// sk_dag_stem_kernel, which is ordered behind it: the kernel boundary makes
+// the tables visible to every workgroup.
 template <int MAXK>
 __global__ void __launch_bounds__(64 * StemWaves<MAXK>::value) sk_gamma_table_kernel(StemLaunch P) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -1164,8 +1260,14 @@ __global__ void __launch_bounds__(64 * StemWaves<MAXK>::value) sk_gamma_table_ke
   __syncthreads();
   YView Y;
   stage_y<MAXK>(P, L, P.slot_y[slot], Y);
-  gamma_rows<MAXK>(P, Y, R, L.co, L.gp, P.gam + (size_t)slot * P.gam_doubles,
-                   P.kap_y + (size_t)slot * P.xset.n_gam, wave_u, nwaves, lane);
+  double* gamtab = P.gam + (size_t)slot * P.gam_doubles;
+  gamma_rows<MAXK>(P, Y, R, L.co, L.gp, gamtab, P.kap_y + (size_t)slot * P.xset.n_gam, wave_u, nwaves, lane);
+  if (P.phi_shared) {
+    __syncthreads();  // the Gamma table, for every wave's phi keys
+    double* phitab = P.phi + (size_t)slot * P.phi_doubles;
+    phi_rows<MAXK>(P, Y, R, L.co, L.gp, gamtab, phitab, phitab + (size_t)P.xset.n_phi * (64 * MAXK), nullptr, 0,
+                   P.xset.n_phi, wave_u, nwaves, lane);
+  }
 }
 
 template <int MAXK>
@@ -1189,30 +1291,51 @@ __global__ void __launch_bounds__(64 * StemWaves<MAXK>::value) sk_dag_stem_kerne
   lds_f64* hb = L.hball + (size_t)wave * 64 * PW;
   for (int j = 0; j < PW; ++j) hb[64 * j + lane] = 0.0;  // kept zero between MATCH passes
   double* slab = P.scratch + (size_t)(blockIdx.x * nwaves + wave) * P.slab_doubles;
-  // the workgroup's Phi table: n_phi rows of 64*MAXK, then their sums kappa
-  double* phitab = P.phi_on ? P.phi + (size_t)blockIdx.x * P.phi_doubles : nullptr;
-  double* phikap = P.phi_on ? phitab + (size_t)P.xset.n_phi * (64 * MAXK) : nullptr;
-  const int band = (int)P.band;
-
   // wave index as an SGPR value: every branch below on it is wave-uniform
   const int wave_u = __builtin_amdgcn_readfirstlane(wave);
+  // Items come from the queue of the workgroup's XCD (workgroups go to the
+  // XCDs round-robin, so blockIdx.x % 8 names the ones that share an L2: a
+  // placement guess that costs L2 hits, never results, when wrong), and from
+  // the following queues once that one is empty (a queue found empty stays
+  // empty: the count in ctl[2], thread 0's, only grows).  Atomic counters
+  // only; nobody waits for anybody.
+  if (threadIdx.x == 0) ctl[2] = 0;
   for (;;) {
     __syncthreads();
-    if (threadIdx.x == 0) ctl[0] = atomicAdd(P.item_counter, 1);
+    if (threadIdx.x == 0) {
+      int got = -1, qk = ctl[2];
+      while (qk < kStemQueues) {
+        const int q = (blockIdx.x + qk) % kStemQueues;
+        const int i = P.queue_off[q] + atomicAdd(P.item_counter + q, 1);
+        if (i < P.queue_off[q + 1]) {
+          got = i;
+          break;
+        }
+        ++qk;
+      }
+      ctl[0] = got;
+      ctl[2] = qk;
+    }
     __syncthreads();
     const int it = __builtin_amdgcn_readfirstlane(ctl[0]);
-    if (it >= P.n_items) break;
-    const int4 item = P.items[it];  // {y, base, count, Gamma table slot}
+    if (it < 0) break;
+    const int4 item = P.items[it];  // {y, base, count, table slot}
     const int y = item.x;
     YView Y;
     stage_y<MAXK>(P, L, y, Y);
-    const int nb = Y.nb, bb = Y.bb;
 
     // Gamma rows of this y (gapless y only): the y's shared table, built by
     // sk_gamma_table_kernel (its sums kappa into LDS), or this workgroup's
     // own, built here
     const bool gam = P.gam_on && s.ex_gapless[y];
     double* gamtab = nullptr;
+    // the Phi table of this y (phi_shared: of its slot; never read without
+    // one): n_phi rows of 64*MAXK, then their sums kappa.  (The index through
+    // readfirstlane: a pointer the compiler cannot prove uniform costs the
+    // row loop registers -- 25 spilled VGPRs for 7 in the MAXK 16 class.)
+    const int tslot = __builtin_amdgcn_readfirstlane(P.phi_shared ? item.w : (int)blockIdx.x);
+    double* phitab = P.phi + (int64_t)tslot * P.phi_doubles;
+    double* phikap = P.phi_on ? phitab + (size_t)P.xset.n_phi * (64 * MAXK) : nullptr;
     if (gam) {
       const DevSet& xset = P.xset;
       if (P.gam_shared) {
@@ -1225,87 +1348,11 @@ __global__ void __launch_bounds__(64 * StemWaves<MAXK>::value) sk_dag_stem_kerne
       }
       __syncthreads();  // the table and kappa, for every wave's pairs
 
-      // Phi rows of the item's phi keys t = (code a, len, gamma key g):
-      // M_t[q] = co[a][bp(q)] p(q) sum_{cy in ch(q)} g^gy Gamma_g[cy] over
-      // the y stems q in len's band; Phi_t = its IY sweep; kappa_t = sum_q
-      // M_t[q] P_y[q] (a phi row's MATCH row is pf_p sum_c w_c M_{t(c)} plus
-      // its Gamma_{a,len} part)
-      if (P.phi_on) {
-        // the item's keys come sorted by gamma key: wave w takes the w-th
-        // contiguous share, and H_g[q] = sum_{cy in ch(q)} g^gy Gamma_g[cy]
-        // (independent of the key's code and length) is formed once per
-        // gamma key from the Gamma row staged in the wave's LDS row
-        const DevSet& xset = P.xset;
-        const int pb = P.item_phi_off[it], pe = P.item_phi_off[it + 1];
-        const int share = (pe - pb + nwaves - 1) / nwaves;
-        const int t0 = pb + wave_u * share, t1 = min(pe, t0 + share);
-        int gcur = -1;
-        double Hr[MAXK];
-#pragma unroll
-        for (int k = 0; k < MAXK; ++k) Hr[k] = 0.0;
-        for (int t = t0; t < t1; ++t) {
-          const int idx = __builtin_amdgcn_readfirstlane(P.item_phi[t]);
-          const int g = __builtin_amdgcn_readfirstlane((int)xset.phi_g[idx]);
-          if (g != gcur) {
-            gcur = g;
-            const double* __restrict__ grow = gamtab + (size_t)g * (64 * MAXK);
-#pragma unroll
-            for (int k = 0; k < MAXK; ++k) R[lane + 64 * k] = grow[lane + 64 * k];
-            wave_sync();
-            for (int k = 0; k < MAXK; ++k) {
-              const int q = lane + 64 * k;
-              double H = 0.0;
-              if (q < Y.nl) {
-                const uint32_t na = Y.nrg[q].x;
-                const int ne = (int)((na >> 16) & 0xff), e0 = (int)(na & 0xffff);
-                for (int e = 0; e < ne; ++e) {
-                  const uint32_t rec = edges_global<MAXK>() ? Y.ed2g[e0 + e] : Y.ed2[e0 + e];
-                  H += gp[rec >> 22] * R[rec & 0x7ff];
-                }
-              }
-              Hr[k] = H;
-            }
-            wave_sync();
-          }
-          const uint32_t al = xset.phi_al[idx];
-          const int acode = (int)(al >> 16) * 16, alen = (int)(al & 0xffff);
-          double kp = 0.0;
-#pragma unroll
-          for (int k = 0; k < MAXK; ++k) {
-            const int q = lane + 64 * k;
-            double M = 0.0;
-            if (q < Y.nl) {
-              const uint4 nd = Y.nrg[q];
-              const int ylen = (int)(s.yn_b[nb + q] & 0xffff);
-              if (Hr[k] != 0.0 && (band == 0 || abs(alen - ylen) <= band)) {
-                double vs;
-                if ((nd.y >> 24) != 0u) {
-                  vs = co[acode + ((nd.y >> 16) & 0xf)] * (double)__uint_as_float(nd.w);
-                } else {
-                  vs = 0.0;
-                  const int yb0 = (int)(s.yn_b[nb + q] >> 16), ynb = (int)(nd.x >> 24);
-                  for (int b = 0; b < ynb; ++b)
-                    vs += co[acode + s.bpf_code[bb + yb0 + b]] * (double)s.bpf_p[bb + yb0 + b];
-                }
-                M = vs * Hr[k];
-                kp += M * s.yn_P[nb + q];
-              }
-            }
-            R[q] = M;
-          }
-          for (int off = 32; off > 0; off >>= 1) kp += __shfl_xor(kp, off, 64);
-          if (lane == 0) phikap[idx] = kp;
-          wave_sync();
-          int c0 = 0;
-          if (band > 0) c0 = Y.ycs[min(max(alen - band, 0), Y.lmax + 1)];
-          c0 = __builtin_amdgcn_readfirstlane(c0);
-          if (c0 < Y.nch) iy_sweep<node_weights<MAXK>(), node_weights_f32<MAXK>()>(Y, R, c0, lane);
-          double* prow = phitab + (size_t)idx * (64 * MAXK);
-#pragma unroll
-          for (int k = 0; k < MAXK; ++k)
-            if (lane + 64 * k < Y.nl) prow[lane + 64 * k] = R[lane + 64 * k];
-          wave_sync();
-        }
+      // Phi rows: the y's shared table (sk_gamma_table_kernel: every phi key
+      // of the x set), or this workgroup's own, the item's phi keys built here
+      if (P.phi_on && !P.phi_shared) {
+        phi_rows<MAXK>(P, Y, R, co, gp, gamtab, phitab, phikap, P.item_phi, P.item_phi_off[it],
+                       P.item_phi_off[it + 1], wave_u, nwaves, lane);
         __syncthreads();
       }
     }

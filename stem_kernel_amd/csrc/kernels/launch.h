@@ -10,6 +10,8 @@
 
 namespace sk {
 
+constexpr int kStemQueues = 8;  // item queues of a stem class launch: one per XCD
+
 struct StemLaunch {
   DevSet xset;        // row examples (x role)
   DevSet yset;        // column examples (y role); may equal xset
@@ -29,7 +31,13 @@ struct StemLaunch {
   const int32_t* xs = nullptr;
   const int64_t* oidx = nullptr;
   double* out = nullptr;
+  // item queues: queue q holds the items [queue_off[q], queue_off[q + 1]) and
+  // is pulled through item_counter[q]; a workgroup starts at queue
+  // blockIdx.x % kStemQueues (the workgroups that share an XCD's L2 share a
+  // queue, so they work on the same y's) and goes on to the next queues when
+  // its own is empty
   int* item_counter = nullptr;
+  int32_t queue_off[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
   double* scratch = nullptr;   // per-wave G0 slabs
   int64_t slab_doubles = 0;
   // Gamma rows (gam_on: the x set has gamma keys): tables of xset.n_gam rows
@@ -45,14 +53,18 @@ struct StemLaunch {
   double* kap_y = nullptr;            // n_slots x xset.n_gam (gam_shared)
   const int32_t* slot_y = nullptr;    // n_slots (device; gam_shared)
   int32_t n_slots = 0;
-  // Phi rows (phi_on: the x set has phi keys): per-workgroup table of
-  // xset.n_phi rows of 64*MAXK doubles and their n_phi sums; the item's phi
-  // keys item_phi[item_phi_off[it] .. item_phi_off[it + 1])
+  // Phi rows (phi_on: the x set has phi keys): tables of xset.n_phi rows of
+  // 64*MAXK doubles and their n_phi sums.  phi_shared (only with gam_shared):
+  // one table per Gamma table slot, every phi key of the x set, written by
+  // sk_gamma_table_kernel behind the slot's Gamma rows.  Else one table per
+  // workgroup, the item's phi keys item_phi[item_phi_off[it] ..
+  // item_phi_off[it + 1]) rebuilt for every item
   double* phi = nullptr;
-  int64_t phi_doubles = 0;  // per workgroup
+  int64_t phi_doubles = 0;  // per table
   const int32_t* item_phi_off = nullptr;
   const int32_t* item_phi = nullptr;
   int32_t phi_on = 0;
+  int32_t phi_shared = 0;
   unsigned long long* stamps = nullptr;  // diagnostic builds (SK_STAMPS) only
 };
 

@@ -422,7 +422,7 @@ struct sk_context {
   // bit MAXK/4 per DAG stem register class; bit log2(CPL) (+4 when banded)
   // per 4-D stem class
   uint32_t last_stem_classes = 0, last_s4d_classes = 0;
-  int32_t last_gamma_shared = 0;  // class launches of the last call that read shared Gamma tables
+  int32_t last_gamma_shared = 0;  // class launches of the last call that read shared Gamma (and Phi) tables
   uint32_t last_la_protein = 0;   // protein LA kernels of the last call: 1 code, 2 profile
   // RCCL communicator of sk_comm_init (ncclComm_t, csrc/host/shard.cpp)
   void* comm = nullptr;
@@ -2806,6 +2806,8 @@ int run_pairs(sk_context* ctx, sk_dataset* xs_, sk_dataset* ys_, const sk_kernel
     size_t item_off = 0, n_items = 0;
     size_t slot_off = 0, n_slots = 0;         // the class's Gamma table slots in slot_y
     bool gam_shared = false;                  // one Gamma table per y (else per workgroup)
+    bool phi_shared = false;                  // ... and one Phi table per y (else per workgroup and item)
+    int32_t queue_off[sk::kStemQueues + 1] = {};  // the item queues' ranges, from item_off
     size_t tab_off = 0;                       // its tables in the scratch's table region (doubles)
   };
   std::vector<StemClass> classes;
@@ -2934,30 +2936,59 @@ int run_pairs(sk_context* ctx, sk_dataset* xs_, sk_dataset* ys_, const sk_kernel
       C.grid = ctx->n_cu * per_cu;
       // Work items = pairs of one y (the workgroup stages one y DAG in LDS
       // and waits for its slowest wave at every item boundary, about half a
-      // pair per wave).  Guided self-scheduling: the y's are taken largest
-      // column first and each item is 1/(K * grid) of the class's remaining
-      // cost (at least one round of W pairs), so the first items are large
-      // (few boundaries) and the last ones a round each (short launch tail).
-      // Items are pulled in this order (K = 1.5; NS 161k pairs/s at K = 1,
-      // 160.8k at 1.5, 160.0k at 2, 157.2k at 8; C2 148k at 1.5, 140k at 1).
-      // A gapless y of a launch with gamma keys gets a Gamma table slot,
-      // carried in its items' .w (-1: none).
+      // pair per wave).  Whole y columns are dealt to eight item queues, one
+      // per XCD (the workgroups blockIdx.x % 8 == q pull from queue q and
+      // share an L2: the fewer y's they are on at a time, the more of the
+      // Gamma, Phi and node-record reads hit it): by cost, largest first onto
+      // the least-loaded queue, a queue's columns in that order.  Inside a
+      // queue, guided self-scheduling: each item is 1/(K * grid / 8) of the
+      // queue's remaining cost (at least one round of W pairs), so the first
+      // items are large (few boundaries) and the last ones a round each (short
+      // launch tail) -- and at most 1/8 of its column's cost, so that the
+      // queue's workgroups stand on a few y's, not on one each.  (K = 1.5; NS
+      // 161k pairs/s at K = 1, 160.8k at 1.5, 160.0k at 2, 157.2k at 8; C2
+      // 148k at 1.5, 140k at 1.)  A workgroup whose queue is empty takes from
+      // the others (dag_stem.hip).
+      // A gapless y of a launch with gamma keys gets a table slot (Gamma and
+      // Phi), carried in its items' .w (-1: none).
       std::vector<int> ysel;
-      double class_cost = 0.0;
+      std::vector<double> ycost(ny, 0.0);
       for (int j = 0; j < ny; ++j) {
         if (cnt[j + 1] == cnt[j] || !in_class(j, maxk)) continue;
         ysel.push_back(j);
         for (int64_t t = cnt[j]; t < cnt[j + 1]; ++t)
-          class_cost += (double)PX.ex_nl[x[byy[t]]] * (double)PY.ex_nl[j];
+          ycost[j] += (double)PX.ex_nl[x[byy[t]]] * (double)PY.ex_nl[j];
       }
       std::stable_sort(ysel.begin(), ysel.end(), [&](int a, int b) {
         return cnt[a + 1] - cnt[a] > cnt[b + 1] - cnt[b];
       });
       double gss_k = 1.5;  // tuning knob: SK_GSS_K (items per workgroup at the start)
       if (const char* e = SK_KNOB("SK_GSS_K")) gss_k = std::max(0.25, std::atof(e));
+      int nq = sk::kStemQueues;  // SK_ITEM_QUEUES=1: one queue, uncapped items
+      if (const char* e = SK_KNOB("SK_ITEM_QUEUES")) nq = std::min(std::max(std::atoi(e), 1), sk::kStemQueues);
+      double cap = nq > 1 ? 1.0 / 8.0 : 1.0;  // an item's largest share of its column (SK_ITEM_CAP: 1 / share)
+      if (const char* e = SK_KNOB("SK_ITEM_CAP")) cap = 1.0 / std::max(1.0, std::atof(e));
+      std::vector<int> qof(ny, 0);  // column -> queue
+      double class_cost = 0.0;
+      {
+        std::vector<int> bycost(ysel);
+        if (nq > 1)
+          std::stable_sort(bycost.begin(), bycost.end(), [&](int a, int b) { return ycost[a] > ycost[b]; });
+        std::vector<double> load(nq, 0.0);
+        for (int j : bycost) {
+          const int q = (int)(std::min_element(load.begin(), load.end()) - load.begin());
+          qof[j] = q;
+          load[q] += ycost[j];
+          class_cost += ycost[j];
+        }
+      }
+      // the items in the class's one guided order (their sizes fall over the
+      // whole launch, so every queue ends in short items and the workgroups
+      // that come over from an empty queue find a fine-grained tail), each
+      // into its column's queue
+      std::vector<std::vector<int4>> qitems(nq);
       const double share = 1.0 / (gss_k * (double)C.grid);
       double remaining = class_cost;
-      C.item_off = items.size();
       for (int j : ysel) {
         const double yw = (double)PY.ex_nl[j];
         int slot = -1;
@@ -2967,7 +2998,7 @@ int run_pairs(sk_context* ctx, sk_dataset* xs_, sk_dataset* ys_, const sk_kernel
         }
         int64_t b = cnt[j];
         while (b < cnt[j + 1]) {
-          const double target = remaining * share;
+          const double target = std::min(remaining * share, ycost[j] * cap);
           int64_t e = b;
           double cost = 0.0;
           // whole rounds of W pairs until the target cost is reached
@@ -2976,11 +3007,17 @@ int run_pairs(sk_context* ctx, sk_dataset* xs_, sk_dataset* ys_, const sk_kernel
             for (int64_t t = e; t < re; ++t) cost += (double)PX.ex_nl[x[byy[t]]] * yw;
             e = re;
           }
-          items.push_back(make_int4(j, (int)b, (int)(e - b), slot));
+          qitems[qof[j]].push_back(make_int4(j, (int)b, (int)(e - b), slot));
           remaining -= cost;
           b = e;
         }
       }
+      C.item_off = items.size();
+      for (int q = 0; q < sk::kStemQueues; ++q) {
+        C.queue_off[q] = (int32_t)(items.size() - C.item_off);
+        if (q < nq) items.insert(items.end(), qitems[q].begin(), qitems[q].end());
+      }
+      C.queue_off[sk::kStemQueues] = (int32_t)(items.size() - C.item_off);
       C.n_slots = slot_y.size() - C.slot_off;
       C.n_items = items.size() - C.item_off;
       C.grid = (int)std::min<int64_t>(C.grid, std::max<int64_t>(1, (int64_t)C.n_items));
@@ -2992,16 +3029,127 @@ int run_pairs(sk_context* ctx, sk_dataset* xs_, sk_dataset* ys_, const sk_kernel
   }
 
   if (host_stats) th1 = now_ms();
-  // the items' phi keys (the union over their x's; gapless y only), for the
-  // workgroups' Phi tables (dag_stem.hip)
   std::vector<int32_t> item_phi_off, item_phi;
   const bool phi_on = stem && !PX.phi_al.empty() && !PX.gam_key.empty();
-  if (phi_on) {
+  bool two_streams = false;
+  double *scratch_cls = nullptr, *scratch_tab = nullptr;
+  int64_t big_stride = 0, big_wave = 0;
+  int big_grid = 0;
+  if (stem) {
+    // class c runs on the main stream (c even) or the class stream (c odd):
+    // one scratch region per stream, serving its classes in turn
+    two_streams = classes.size() > 1 && !SK_KNOB("SK_SERIAL_CLASSES");
+    size_t scratch_need = 0, scratch_x = 0;
+    // The Gamma and Phi tables of a class launch: one of each per gapless y
+    // of the launch, written by the table kernel and read by every workgroup
+    // on that y, if they fit a budget taken from free memory (a quarter of
+    // it, the scratch held so far counted as free, 8 GiB at most;
+    // SK_GAM_TABLE_MB: the budget in MB, 0 = never): first the Gamma tables
+    // of the call's classes, in class order, then with what is left their
+    // Phi tables (every phi key of the x set: n_phi rows per y, 11 MB for an
+    // NS y; SK_PHI_TABLE_MB: their own budget in MB); else one per workgroup,
+    // rebuilt per item (the Phi tables only behind shared Gamma tables).
+    // The table kernels of all classes run first (below), so every class has
+    // table memory of its own, past the two streams' regions.  Free memory is
+    // asked for only when the tables do not fit the scratch the context
+    // already holds, and if the scratch cannot be had with them, the call
+    // goes on without (below).
+    size_t tab_total = 0;
+    size_t phi_budget = SIZE_MAX;
+    if (const char* e = SK_KNOB("SK_PHI_TABLE_MB")) phi_budget = (size_t)std::max(0.0, std::atof(e) * 1048576.0);
+    auto size_classes = [&](size_t gam_budget) {
+      scratch_need = scratch_x = tab_total = 0;
+      // the Gamma tables: per y of the launch (and their sums), or per workgroup
+      auto gam_bytes = [&](const StemClass& C) {
+        return C.n_slots * (size_t)PX.gam_key.size() * (size_t)(64 * C.maxk + 1) * sizeof(double);
+      };
+      // the Phi tables and sums likewise
+      auto phi_bytes = [&](const StemClass& C) {
+        return phi_on ? C.n_slots * (size_t)PX.phi_al.size() * (size_t)(64 * C.maxk + 1) * sizeof(double) : 0;
+      };
+      size_t total = 0, phi_total = 0;
+      for (StemClass& C : classes) {
+        C.gam_shared = C.n_slots > 0 && total + gam_bytes(C) <= gam_budget;
+        if (C.gam_shared) total += gam_bytes(C);
+      }
+      for (StemClass& C : classes) {
+        C.phi_shared = phi_on && C.gam_shared && total + phi_bytes(C) <= gam_budget &&
+                       phi_total + phi_bytes(C) <= phi_budget;
+        if (C.phi_shared) {
+          total += phi_bytes(C);
+          phi_total += phi_bytes(C);
+        }
+      }
+      for (size_t c = 0; c < classes.size(); ++c) {
+        StemClass& C = classes[c];
+        if (C.gam_shared) {
+          C.tab_off = tab_total / sizeof(double);
+          tab_total += gam_bytes(C) + (C.phi_shared ? phi_bytes(C) : 0);
+        }
+        // + one junk row: root rows are stored there (never read)
+        const int64_t slab = (int64_t)(PX.max_slots + 1) * 64 * C.maxk;
+        const int64_t gtab1 = (int64_t)PX.gam_key.size() * 64 * C.maxk;
+        const int64_t ptab = phi_on ? (int64_t)PX.phi_al.size() * (64 * C.maxk + 1) : 0;
+        const size_t b = (size_t)C.grid *
+                         (C.nwaves * slab + (C.phi_shared ? 0 : ptab) + (C.gam_shared ? 0 : gtab1)) * sizeof(double);
+        size_t& r = (two_streams && (c & 1)) ? scratch_x : scratch_need;
+        r = std::max(r, b);
+      }
+    };
+    const bool any_slots = !PX.gam_key.empty() && !slot_y.empty();
+    size_classes(any_slots ? SIZE_MAX : 0);
+    if (const char* e = SK_KNOB("SK_GAM_TABLE_MB")) {
+      size_classes((size_t)std::max(0.0, std::atof(e) * 1048576.0));
+    } else if (tab_total > 0 && scratch_need + scratch_x + tab_total + 512 > ctx->scratch_bytes) {
+      size_t free_b = 0, total_b = 0;
+      SK_HIP(ctx, hipMemGetInfo(&free_b, &total_b));
+      size_classes(std::min<size_t>((free_b + ctx->scratch_bytes) / 4, (size_t)8 << 30));
+    }
+    // big-y kernel: per wave S, G1 and the G0 slots, rows of `big_stride`
+    // doubles; as many waves as pairs, the grid, and a scratch budget allow
+    big_stride = ((int64_t)std::max(big_max_nl, 1) + 63) / 64 * 64;
+    big_wave = (int64_t)(PX.max_slots + 2) * big_stride;
+    if (!big_x.empty()) {
+      size_t free_b = 0, total_b = 0;
+      SK_HIP(ctx, hipMemGetInfo(&free_b, &total_b));
+      const size_t budget = std::max<size_t>(std::min<size_t>(free_b / 2, (size_t)32 << 30),
+                                             (size_t)big_wave * 8 * sk::kStemBigWaves);
+      const int64_t by_mem = (int64_t)(budget / ((size_t)big_wave * 8 * sk::kStemBigWaves));
+      const int64_t by_pairs = ((int64_t)big_x.size() + sk::kStemBigWaves - 1) / sk::kStemBigWaves;
+      big_grid = (int)std::max<int64_t>(1, std::min<int64_t>({by_mem, by_pairs, (int64_t)ctx->n_cu * 8}));
+      scratch_need = std::max(scratch_need,
+                              (size_t)big_grid * sk::kStemBigWaves * (size_t)big_wave * sizeof(double));
+    }
+    const size_t big_need = scratch_need;  // (>= the classes' need on the main stream)
+    auto get_scratch = [&]() {
+      scratch_need = (std::max(scratch_need, big_need) + 255) / 256 * 256;
+      scratch_x = (scratch_x + 255) / 256 * 256;
+      return ensure_scratch(ctx, std::max<size_t>(scratch_need + scratch_x + tab_total, 64));
+    };
+    rc = get_scratch();
+    if (rc && tab_total > 0) {  // not with the shared tables: per-workgroup tables then
+      (void)hipGetLastError();
+      size_classes(0);
+      rc = get_scratch();
+    }
+    if (rc) return rc;
+    scratch_cls = ctx->scratch + scratch_need / sizeof(double);
+    scratch_tab = scratch_cls + scratch_x / sizeof(double);
+  }
+  // the items' phi keys (the union over their x's; gapless y only), for the
+  // workgroups' Phi tables (dag_stem.hip) of the class launches that do not
+  // share theirs (none otherwise: no unions, no uploads)
+  bool phi_items = false;
+  for (const StemClass& C : classes) phi_items = phi_items || (phi_on && !C.phi_shared);
+  if (phi_items) {
     // union of the x's key bitsets, keys ordered by gamma key (the kernel
     // forms one H row per gamma key and wave)
     // (contiguous item ranges on host threads, concatenated in item order)
     const size_t W = (PX.phi_al.size() + 63) / 64;
     const size_t ni = items.size();
+    std::vector<uint8_t> own(ni, 0);  // items of launches with per-workgroup Phi tables
+    for (const StemClass& C : classes)
+      if (!C.phi_shared) std::fill(own.begin() + C.item_off, own.begin() + C.item_off + C.n_items, 1);
     const int T = plan_threads((int)(ni / 512 + 1));
     std::vector<std::vector<int32_t>> tkeys(T), tcnt(T);
     run_slices(T, [&](int t) {
@@ -3009,7 +3157,7 @@ int run_pairs(sk_context* ctx, sk_dataset* xs_, sk_dataset* ys_, const sk_kernel
       for (size_t i = ni * t / T; i < ni * (t + 1) / T; ++i) {
         const int4 it = items[i];
         const size_t k0 = tkeys[t].size();
-        if (PY.ex_gapless[it.x]) {
+        if (own[i] && PY.ex_gapless[it.x]) {
           std::fill(acc.begin(), acc.end(), 0ull);
           for (int u = it.y; u < it.y + it.z; ++u) {
             const uint64_t* b = PX.ex_phi_bits.data() + (size_t)ixs[u] * W;
@@ -3027,10 +3175,17 @@ int run_pairs(sk_context* ctx, sk_dataset* xs_, sk_dataset* ys_, const sk_kernel
       item_phi.insert(item_phi.end(), tkeys[t].begin(), tkeys[t].end());
       for (int32_t c : tcnt[t]) item_phi_off.push_back(item_phi_off.back() + c);
     }
-    if (std::getenv("SK_PHI_STATS"))
-      std::fprintf(stderr, "[phi] keys=%zu items=%zu item keys=%zu pairs=%lld phi components=%zu rows=%zu\n",
-                   PX.phi_al.size(), items.size(), item_phi.size(), (long long)n, PX.phk_idx.size(),
-                   PX.xgrow.size());
+  }
+  if (phi_on && std::getenv("SK_PHI_STATS")) {
+    size_t shared = 0, slots = 0;
+    for (const StemClass& C : classes) {
+      shared += C.phi_shared ? 1 : 0;
+      slots += C.phi_shared ? C.n_slots : 0;
+    }
+    std::fprintf(stderr, "[phi] keys=%zu items=%zu item keys=%zu pairs=%lld phi components=%zu rows=%zu "
+                 "classes=%zu sharing=%zu tables=%zu\n",
+                 PX.phi_al.size(), items.size(), item_phi.size(), (long long)n, PX.phk_idx.size(),
+                 PX.xgrow.size(), classes.size(), shared, slots);
   }
 
   if (host_stats) th2 = now_ms();
@@ -3076,7 +3231,7 @@ int run_pairs(sk_context* ctx, sk_dataset* xs_, sk_dataset* ys_, const sk_kernel
   need += soidx.size() * 8 + n_str_pos * (2 * sizeof(sk::StrPos) + sizeof(sk::StrCode)) + 1024;
   need += (item_phi_off.size() + item_phi.size()) * 4 + 512;
   need += 256 * 8 + 16 * 8 + (size_t)(max_len + 4) * 8 * 2;
-  need += 1024;
+  need += 1024 + 256;
   need += items.size() * sizeof(int4) + nb * (4 + 8) + nb * 8 * 2 + nb * 4 * 2 + 64 + 8 * 256;
   need += slot_y.size() * 4 + 256;
   need += big_x.size() * (4 + 4 + 8) + 3 * 256;
@@ -3095,7 +3250,7 @@ int run_pairs(sk_context* ctx, sk_dataset* xs_, sk_dataset* ys_, const sk_kernel
   double* d_str = A.take<double>(nb);
   int32_t* d_px = A.take<int32_t>(nb);
   int32_t* d_py = A.take<int32_t>(nb);
-  int* d_ctr = A.take<int>(64);
+  int* d_ctr = A.take<int>(128);  // 16, then kStemQueues item counters per stem class
   int32_t* d_sloty = A.take<int32_t>(std::max<size_t>(slot_y.size(), 1));
   int32_t* d_bx = A.take<int32_t>(std::max<size_t>(big_x.size(), 1));
   int32_t* d_by = A.take<int32_t>(std::max<size_t>(big_x.size(), 1));
@@ -3122,7 +3277,7 @@ int run_pairs(sk_context* ctx, sk_dataset* xs_, sk_dataset* ys_, const sk_kernel
   SK_HIP(ctx, sk::h2d(ctx, d_st, st.data(), 16 * 8, S));
   SK_HIP(ctx, sk::h2d(ctx, d_gp_loop, gl.data(), gl.size() * 8, S));
   SK_HIP(ctx, sk::h2d(ctx, d_gp_str, gs.data(), gs.size() * 8, S));
-  SK_HIP(ctx, hipMemsetAsync(d_ctr, 0, 64 * sizeof(int), S));
+  SK_HIP(ctx, hipMemsetAsync(d_ctr, 0, 128 * sizeof(int), S));
 
   double* stem_out = (combine_mode(kp->kind) == sk::kCombineStem) ? out_dev : d_stem;
   double* str_out = (combine_mode(kp->kind) == sk::kCombineStr) ? out_dev : d_str;
@@ -3145,7 +3300,7 @@ int run_pairs(sk_context* ctx, sk_dataset* xs_, sk_dataset* ys_, const sk_kernel
     SK_HIP(ctx, sk::h2d(ctx, d_ixs, ixs.data(), nb * 4, S));
     SK_HIP(ctx, sk::h2d(ctx, d_oidx, ioidx.data(), nb * 8, S));
     SK_HIP(ctx, sk::h2d(ctx, d_sloty, slot_y.data(), slot_y.size() * 4, S));
-    if (phi_on) {
+    if (phi_items) {
       SK_HIP(ctx, sk::h2d(ctx, d_iphi_off, item_phi_off.data(), item_phi_off.size() * 4, S));
       if (!item_phi.empty())
         SK_HIP(ctx, sk::h2d(ctx, d_iphi, item_phi.data(), item_phi.size() * 4, S));
@@ -3176,83 +3331,6 @@ int run_pairs(sk_context* ctx, sk_dataset* xs_, sk_dataset* ys_, const sk_kernel
       SK_HIP(ctx, sk::launch_prep(xs_->dev, pn, d_gp_loop, gap2, S));
       xs_->prep_loop_gap = kp->loop_gap;
     }
-    // class c runs on the main stream (c even) or the class stream (c odd):
-    // one scratch region per stream, serving its classes in turn
-    const bool two_streams = classes.size() > 1 && !SK_KNOB("SK_SERIAL_CLASSES");
-    size_t scratch_need = 0, scratch_x = 0;
-    // The Gamma tables of a class launch: one per gapless y of the launch,
-    // written by the table kernel and read by every workgroup on that y, if
-    // the tables of the call's classes so far and this one's fit a budget
-    // taken from free memory (a quarter of it, the scratch held so far
-    // counted as free, 8 GiB at most; SK_GAM_TABLE_MB: the budget in MB, 0 =
-    // never); else one per workgroup, rebuilt per item.  The table kernels of
-    // all classes run first (below), so every class has table memory of its
-    // own, past the two streams' regions.  Free memory is asked for only
-    // when the tables do not fit the scratch the context already holds, and
-    // if the scratch cannot be had with them, the call goes on without
-    // (below).
-    size_t tab_total = 0;
-    auto size_classes = [&](size_t gam_budget) {
-      scratch_need = scratch_x = tab_total = 0;
-      for (size_t c = 0; c < classes.size(); ++c) {
-        StemClass& C = classes[c];
-        // + one junk row: root rows are stored there (never read)
-        const int64_t slab = (int64_t)(PX.max_slots + 1) * 64 * C.maxk;
-        // + the Gamma tables: per y of the launch (and their sums), or per workgroup
-        const int64_t gtab1 = (int64_t)PX.gam_key.size() * 64 * C.maxk;
-        const size_t shared_b = C.n_slots * (size_t)(gtab1 + (int64_t)PX.gam_key.size()) * sizeof(double);
-        C.gam_shared = C.n_slots > 0 && tab_total + shared_b <= gam_budget;
-        if (C.gam_shared) {
-          C.tab_off = tab_total / sizeof(double);
-          tab_total += shared_b;
-        }
-        // + their Phi tables and sums
-        const int64_t ptab = phi_on ? (int64_t)PX.phi_al.size() * (64 * C.maxk + 1) : 0;
-        const size_t b = (size_t)C.grid * (C.nwaves * slab + ptab + (C.gam_shared ? 0 : gtab1)) * sizeof(double);
-        size_t& r = (two_streams && (c & 1)) ? scratch_x : scratch_need;
-        r = std::max(r, b);
-      }
-    };
-    const bool any_slots = !PX.gam_key.empty() && !slot_y.empty();
-    size_classes(any_slots ? SIZE_MAX : 0);
-    if (const char* e = SK_KNOB("SK_GAM_TABLE_MB")) {
-      size_classes((size_t)std::max(0.0, std::atof(e) * 1048576.0));
-    } else if (tab_total > 0 && scratch_need + scratch_x + tab_total + 512 > ctx->scratch_bytes) {
-      size_t free_b = 0, total_b = 0;
-      SK_HIP(ctx, hipMemGetInfo(&free_b, &total_b));
-      size_classes(std::min<size_t>((free_b + ctx->scratch_bytes) / 4, (size_t)8 << 30));
-    }
-    // big-y kernel: per wave S, G1 and the G0 slots, rows of `big_stride`
-    // doubles; as many waves as pairs, the grid, and a scratch budget allow
-    const int64_t big_stride = ((int64_t)std::max(big_max_nl, 1) + 63) / 64 * 64;
-    const int64_t big_wave = (int64_t)(PX.max_slots + 2) * big_stride;
-    int big_grid = 0;
-    if (!big_x.empty()) {
-      size_t free_b = 0, total_b = 0;
-      SK_HIP(ctx, hipMemGetInfo(&free_b, &total_b));
-      const size_t budget = std::max<size_t>(std::min<size_t>(free_b / 2, (size_t)32 << 30),
-                                             (size_t)big_wave * 8 * sk::kStemBigWaves);
-      const int64_t by_mem = (int64_t)(budget / ((size_t)big_wave * 8 * sk::kStemBigWaves));
-      const int64_t by_pairs = ((int64_t)big_x.size() + sk::kStemBigWaves - 1) / sk::kStemBigWaves;
-      big_grid = (int)std::max<int64_t>(1, std::min<int64_t>({by_mem, by_pairs, (int64_t)ctx->n_cu * 8}));
-      scratch_need = std::max(scratch_need,
-                              (size_t)big_grid * sk::kStemBigWaves * (size_t)big_wave * sizeof(double));
-    }
-    const size_t big_need = scratch_need;  // (>= the classes' need on the main stream)
-    auto get_scratch = [&]() {
-      scratch_need = (std::max(scratch_need, big_need) + 255) / 256 * 256;
-      scratch_x = (scratch_x + 255) / 256 * 256;
-      return ensure_scratch(ctx, std::max<size_t>(scratch_need + scratch_x + tab_total, 64));
-    };
-    rc = get_scratch();
-    if (rc && tab_total > 0) {  // not with the shared tables: per-workgroup tables then
-      (void)hipGetLastError();
-      size_classes(0);
-      rc = get_scratch();
-    }
-    if (rc) return rc;
-    double* scratch_cls = ctx->scratch + scratch_need / sizeof(double);
-    double* scratch_tab = scratch_cls + scratch_x / sizeof(double);
 #ifdef SK_STAMPS
     unsigned long long* d_stamps = nullptr;
     SK_HIP(ctx, hipMalloc(&d_stamps, 16 * sizeof(unsigned long long)));
@@ -3286,7 +3364,8 @@ int run_pairs(sk_context* ctx, sk_dataset* xs_, sk_dataset* ys_, const sk_kernel
       SL.xs = d_ixs;
       SL.oidx = d_oidx;
       SL.out = stem_out;
-      SL.item_counter = d_ctr + 16 + (int)c;
+      SL.item_counter = d_ctr + 16 + sk::kStemQueues * (int)c;
+      for (int q = 0; q <= sk::kStemQueues; ++q) SL.queue_off[q] = C.queue_off[q];
       SL.slab_doubles = (int64_t)(PX.max_slots + 1) * SL.lds_max_nl;
       SL.scratch = on_cls ? scratch_cls : ctx->scratch;
       SL.gam_on = !PX.gam_key.empty();
@@ -3299,9 +3378,12 @@ int run_pairs(sk_context* ctx, sk_dataset* xs_, sk_dataset* ys_, const sk_kernel
       SL.gam = C.gam_shared ? scratch_tab + C.tab_off : wg_tab;
       SL.kap_y = SL.gam + C.n_slots * (size_t)SL.gam_doubles;  // (gam_shared: past the class's tables)
       SL.phi_on = phi_on ? 1 : 0;
+      SL.phi_shared = C.phi_shared ? 1 : 0;
       SL.phi_doubles = phi_on ? (int64_t)PX.phi_al.size() * (SL.lds_max_nl + 1) : 0;
-      SL.phi = wg_tab + (C.gam_shared ? 0 : (size_t)C.grid * SL.gam_doubles);
-      SL.item_phi_off = d_iphi_off + C.item_off;
+      // (phi_shared: past the class's Gamma tables and sums)
+      SL.phi = C.phi_shared ? SL.kap_y + C.n_slots * PX.gam_key.size()
+                            : wg_tab + (C.gam_shared ? 0 : (size_t)C.grid * SL.gam_doubles);
+      SL.item_phi_off = d_iphi_off + (phi_items ? C.item_off : 0);
       SL.item_phi = d_iphi;
 #ifdef SK_STAMPS
       SL.stamps = d_stamps;
@@ -3334,7 +3416,7 @@ int run_pairs(sk_context* ctx, sk_dataset* xs_, sk_dataset* ys_, const sk_kernel
       SK_HIP(ctx, sk::lev_mark(ctx, on_cls ? ctx->cls : S));
       SK_HIP(ctx, sk::launch_stem(SL, C.grid, C.nwaves, on_cls ? ctx->cls : S));
       SK_HIP(ctx, sk::lev_mark(ctx, on_cls ? ctx->cls : S));
-      if (C.gam_shared) ++ctx->last_gamma_shared;
+      if (C.gam_shared && (C.phi_shared || !phi_on)) ++ctx->last_gamma_shared;
       ctx->last_stem_classes |= 1u << (C.maxk % 4 ? C.maxk : C.maxk / 4);  // (MAXK 17: bit 17)
     }
     if (two_streams) {
