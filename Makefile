@@ -16,7 +16,7 @@ LINK_LIBS := -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
 HOST_SRC := $(ROOT)stem_kernel_amd/csrc/host/synth.cpp $(ROOT)stem_kernel_amd/csrc/host/example_build.cpp \
             $(ROOT)stem_kernel_amd/csrc/host/readers.cpp $(ROOT)stem_kernel_amd/csrc/host/shard.cpp \
             $(ROOT)stem_kernel_amd/csrc/host/svm_predict.cpp $(ROOT)stem_kernel_amd/csrc/host/fold_host.cpp \
-            $(ROOT)stem_kernel_amd/csrc/host/svm_train.cpp
+            $(ROOT)stem_kernel_amd/csrc/host/svm_train.cpp $(ROOT)stem_kernel_amd/csrc/host/auc_gradient.cpp
 API_SRC := $(ROOT)stem_kernel_amd/csrc/sk_api.cpp
 HIP_SRC := $(ROOT)stem_kernel_amd/csrc/kernels/dag_stem.hip $(ROOT)stem_kernel_amd/csrc/kernels/profile_string.hip \
            $(ROOT)stem_kernel_amd/csrc/kernels/bpla.hip $(ROOT)stem_kernel_amd/csrc/kernels/stem4d.hip \
@@ -24,7 +24,7 @@ HIP_SRC := $(ROOT)stem_kernel_amd/csrc/kernels/dag_stem.hip $(ROOT)stem_kernel_a
            $(ROOT)stem_kernel_amd/csrc/kernels/dag_stem_big.hip $(ROOT)stem_kernel_amd/csrc/kernels/fold.hip \
            $(ROOT)stem_kernel_amd/csrc/kernels/fold_sample.hip $(ROOT)stem_kernel_amd/csrc/kernels/fold_ali.hip \
            $(ROOT)stem_kernel_amd/csrc/kernels/la_protein.hip $(ROOT)stem_kernel_amd/csrc/kernels/simpal.hip \
-           $(ROOT)stem_kernel_amd/csrc/kernels/svm_smo.hip
+           $(ROOT)stem_kernel_amd/csrc/kernels/svm_smo.hip $(ROOT)stem_kernel_amd/csrc/kernels/auc_grad.hip
 HDRS := $(wildcard $(ROOT)stem_kernel_amd/csrc/*/*.h) $(ROOT)include/stem_kernel.h $(ROOT)stem_kernel_amd/csrc/ribosum85_60.inc \
         $(ROOT)stem_kernel_amd/csrc/blosum62.inc
 
@@ -59,6 +59,9 @@ $(BUILD)/host/synth.o: CXXFLAGS += -ffp-contract=off
 # the SMO solver's G update has four roundings, on the host and in the kernel
 $(BUILD)/host/svm_train.o: CXXFLAGS += -ffp-contract=off
 $(BUILD)/kernels/svm_smo.o: HIPFLAGS += -ffp-contract=off
+# the AUC gradient's conjugate gradient amplifies rounding: both paths round every operation alone
+$(BUILD)/host/auc_gradient.o: CXXFLAGS += -ffp-contract=off
+$(BUILD)/kernels/auc_grad.o: HIPFLAGS += -ffp-contract=off
 
 $(LIB): $(HOST_OBJ) $(HIP_OBJ)
 	$(LINK) -o $@ $^ $(LINK_LIBS)
@@ -119,6 +122,7 @@ $(BUILD)/exp/%.o: $(ROOT)stem_kernel_amd/csrc/%.cpp $(HDRS)
 	$(HIPCC) $(CXXFLAGS) -DSK_EXPERIMENTS -D__HIP_PLATFORM_AMD__ -c $< -o $@
 $(BUILD)/exp/host/synth.o: CXXFLAGS += -ffp-contract=off
 $(BUILD)/exp/host/svm_train.o: CXXFLAGS += -ffp-contract=off
+$(BUILD)/exp/host/auc_gradient.o: CXXFLAGS += -ffp-contract=off
 $(EXP_LIB): $(EXP_OBJ) $(HIP_OBJ)
 	$(LINK) -o $@ $^ $(LINK_LIBS)
 .PHONY: exp

@@ -633,6 +633,89 @@ int sk_svm_train_shape(int32_t *bounds, int32_t *n_classes, int32_t *max_train);
 int sk_svm_model_write(const char *path, const double *labels, int32_t n, const int32_t *train,
                        int32_t n_train, const double *alpha, double rho);
 
+/* ------------------------------------------------- cross-validated AUC gradient
+ * Steps 3 to 5 of GradientComputation::compute (optimizer/gradient.cpp:107-156)
+ * for many (fold, C) problems over one Gram K and its derivative matrices
+ * G[p] = dK/d(parameter p): from a trained fold (alpha, rho: sk_svm_train_batch)
+ * and the smoothed AUC's weights delta of its held-out examples, the gradient
+ * of that AUC with respect to C (cg) and to every kernel parameter (fg[p]).
+ * On the GPU one workgroup per problem (csrc/kernels/auc_grad.hip), on the
+ * host one thread per problem (csrc/host/auc_gradient.cpp).
+ *
+ * Arithmetic kept from the reference (y_k = +1 for a label > 0, else -1; a
+ * label 0 is refused; u = the free examples 0 < alpha < C and c = the bound
+ * ones alpha >= C, both in training order: find_support_vectors,
+ * gradient.cpp:368-403; ts = the test list; every sum starts at 0 and adds
+ * its terms in ascending index, as uBLAS's prod and inner_prod do; no fused
+ * multiply-add):
+ *   solve_d (gradient.cpp:405-456), n_free > 0 only:
+ *     P(i,j) = (y_i y_j) K[u_i][u_j], P(i,n_free) = P(n_free,i) = -y_i,
+ *     P(n_free,n_free) = 0; r(i) = sum_j (delta_j y_i) K[u_i][ts_j],
+ *     r(n_free) = 0 - delta_0 - delta_1 ...; K is read by row only.
+ *     d_u = conjugate_gradient(P, r) from 0 (gradient.cpp:622-644): the early
+ *     return when r.r < 1e-10, at most n_free + 1 passes, no guard on w.z (a
+ *     division by zero propagates inf / NaN to the outputs, as it does there).
+ *   calculate_gradient_c (gradient.cpp:511-547):
+ *     q(i) = 0 - sum_j (y_i y_j) K[u_i][c_j], q(n_free) = sum_j y_{c_j};
+ *     cg = (0 + d_u.q) + sum_i sum_j (delta_i y_{c_j}) K[ts_i][c_j], one chain.
+ *   calculate_gradient_p (gradient.cpp:549-620), g = G[p]:
+ *     q(i) = 0 - sum_j ((y_i y_j) g[u_i][c_j]) C, q(n_free) = 0;
+ *     v = prod(P', beta_u), P'(i,j) = (y_i y_j) g[u_i][u_j] with a zero border,
+ *     beta_u = (alpha_u, rho); dpsi(j) = sum_i (delta_i y_j) g[ts_i][t_j];
+ *     fg[p] = (0 + d_u.(q - v)) + (dpsi, 0).(alpha, rho).
+ * The conjugate gradient on this indefinite system amplifies rounding (a
+ * reordered free set moves cg and fg by 1e-5 to 1e-2 relative: DESIGN.md 16),
+ * so both paths keep the order above and agree bit for bit.
+ *
+ * sk_auc_delta is compute_delta (gradient.cpp:159-206): f = the smoothed AUC
+ * of dec over the (positive, negative) pairs of the test list, positives
+ * outer, negatives inner, and delta = df/d(dec); here a label >= 0 counts as
+ * positive, as it does there.  Host only, for both paths: it goes through
+ * libm's exp.  A test list with one class only gives f = 0 and delta = 0. */
+int sk_auc_delta(const double *dec, const double *labels_of_test, int32_t n_test, double *delta_out,
+                 double *f_out);
+typedef struct {
+  const int32_t *train; /* as sk_svm_problem */
+  int32_t n_train;
+  const int32_t *test;
+  int32_t n_test;
+  double C;            /* one C: find_support_vectors has one */
+  const double *alpha; /* n_train, in training order, >= 0 */
+  double rho;
+  const double *delta; /* n_test */
+} sk_auc_problem;
+typedef struct {
+  int32_t n_free, n_bound;
+  int32_t cg_iterations; /* products P w the conjugate gradient formed (0: early return or n_free = 0) */
+  int32_t finite;        /* 0 when cg, an fg or a d_u entry is inf or NaN */
+} sk_auc_info;
+/* gram: n x n row-major; grads: n_params matrices of n x n (may be NULL when
+ * n_params is 0: then only cg is returned); labels: n values.  cg_out has
+ * n_problems entries, fg_out n_problems * n_params (problem-major), info
+ * n_problems.  d_u_out may be NULL; otherwise problem p's slot starts at
+ * sum over q < p of (n_train_q + 1) and receives its n_free + 1 entries of
+ * d_u when n_free > 0 (nothing otherwise; the rest of the slot is not
+ * written).  SK_ERR_INVALID, with nothing launched, for an index outside
+ * [0, n), a label 0 among a problem's examples, C <= 0, n_test < 1,
+ * n_train < 2, an alpha or delta that is not finite (or alpha < 0), or
+ * n_params < 0; SK_ERR_UNSUPPORTED, with nothing launched, when a problem
+ * has more free examples than sk_auc_gradient_shape's max_free (its P would
+ * not fit its share of the scratch).  The kernel launches are counted by
+ * sk_last_launch_ms. */
+int sk_auc_gradient_batch(sk_context *ctx, const double *gram, const double *grads, int32_t n_params,
+                          int32_t n, const double *labels, const sk_auc_problem *problems,
+                          int32_t n_problems, double *cg_out, double *fg_out, double *d_u_out,
+                          sk_auc_info *info);
+/* The same on n_threads host threads (0 = hardware concurrency), any n_free. */
+int sk_auc_gradient_batch_host(const double *gram, const double *grads, int32_t n_params, int32_t n,
+                               const double *labels, const sk_auc_problem *problems, int32_t n_problems,
+                               int32_t n_threads, double *cg_out, double *fg_out, double *d_u_out,
+                               sk_auc_info *info);
+/* The GPU path's shape: n_free <= *lds_free keeps P in LDS, more keeps it in
+ * a device scratch of 8 (n_free + 1)^2 bytes; *max_free is the most one
+ * problem may have; the problems of one launch share *scratch_budget bytes. */
+int sk_auc_gradient_shape(int32_t *lds_free, int32_t *max_free, int64_t *scratch_budget);
+
 /* ---------------------------------------------------------------- diagnostics */
 /* Milliseconds spent in the last compute call's dominant kernel (DAG stem
  * DP), measured with HIP events on the context's stream, and its launch

@@ -9,7 +9,8 @@ from .kernel_matrix import (  # noqa: F401
     format_libsvm, parse_examples, random_sequences, read_examples, simpal_shape,
 )
 from .svm import (  # noqa: F401
-    DEFAULT_MAX_ITER, CrossValidation, SVMSolution, cross_validate, cv_split, svm_train, svm_train_batch,
+    DEFAULT_MAX_ITER, AUCGradient, CrossValidation, SVMSolution, auc_delta, auc_gradient_batch,
+    auc_gradient_shape, auc_objective, cross_validate, cv_split, optimize, svm_train, svm_train_batch,
     svm_train_shape,
 )
 

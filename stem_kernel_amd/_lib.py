@@ -53,6 +53,17 @@ class SvmSolution(C.Structure):  # sk_svm_solution
                 ("n_free", C.c_int32), ("n_bound", C.c_int32)]
 
 
+class AucProblem(C.Structure):  # sk_auc_problem
+    _fields_ = [("train", C.POINTER(C.c_int32)), ("n_train", C.c_int32), ("test", C.POINTER(C.c_int32)),
+                ("n_test", C.c_int32), ("C", C.c_double), ("alpha", C.POINTER(C.c_double)), ("rho", C.c_double),
+                ("delta", C.POINTER(C.c_double))]
+
+
+class AucInfo(C.Structure):  # sk_auc_info
+    _fields_ = [("n_free", C.c_int32), ("n_bound", C.c_int32), ("cg_iterations", C.c_int32),
+                ("finite", C.c_int32)]
+
+
 _P = C.c_void_p
 _I32P = C.POINTER(C.c_int32)
 _U32P = C.POINTER(C.c_uint32)
@@ -170,6 +181,12 @@ SIGNATURES = {
                                           _F64P, _F64P, C.POINTER(SvmSolution)]),
     "sk_svm_train_shape": (C.c_int, [_I32P, _I32P, _I32P]),
     "sk_svm_model_write": (C.c_int, [C.c_char_p, _F64P, C.c_int32, _I32P, C.c_int32, _F64P, C.c_double]),
+    "sk_auc_delta": (C.c_int, [_F64P, _F64P, C.c_int32, _F64P, _F64P]),
+    "sk_auc_gradient_batch": (C.c_int, [_P, _F64P, _F64P, C.c_int32, C.c_int32, _F64P, C.POINTER(AucProblem),
+                                        C.c_int32, _F64P, _F64P, _F64P, C.POINTER(AucInfo)]),
+    "sk_auc_gradient_batch_host": (C.c_int, [_F64P, _F64P, C.c_int32, C.c_int32, _F64P, C.POINTER(AucProblem),
+                                             C.c_int32, C.c_int32, _F64P, _F64P, _F64P, C.POINTER(AucInfo)]),
+    "sk_auc_gradient_shape": (C.c_int, [_I32P, _I32P, C.POINTER(C.c_int64)]),
 }
 
 _lock = threading.Lock()

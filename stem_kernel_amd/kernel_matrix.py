@@ -786,6 +786,16 @@ class Context:
         val, grad = self.bpla_gradients(ds, kernel, iu, ju)
         return assemble_gradients(iu, ju, val, grad, n, normalize)
 
+    def bpla_auc_objective(self, ds: Dataset, kernel: "BPLAKernel", labels, n_folds: int, C: float,
+                           normalize: bool = False, eps: float = 1e-3, max_iter=None):
+        """One step of the bpla_optimizer on this GPU: bpla_gradient_gram,
+        then svm.auc_objective over it (optimizer/optimizer.cpp:45-77).
+        Returns (f, g, records) with g over (C, alpha, beta, gap, ext)."""
+        from . import svm
+        K, G = self.bpla_gradient_gram(ds, kernel, normalize)
+        return svm.auc_objective(K, G, labels, n_folds, C, eps=eps, ctx=self,
+                                 max_iter=svm.DEFAULT_MAX_ITER if max_iter is None else max_iter)
+
     def comm_init(self, uid: bytes, rank: int, world: int) -> None:
         """This context's RCCL communicator (sk_comm_init); uid = the 128
         bytes rank 0 drew with sk_comm_unique_id (see shard.rccl_init)."""

@@ -186,3 +186,166 @@ def cross_validate(K, labels, n_folds: int, Cs, eps: float = 1e-3, max_iter: int
     flat = svm_train_batch(K, labels, ps, ctx=ctx, n_threads=n_threads)
     sols = [flat[k * n_folds:(k + 1) * n_folds] for k in range(len(Cs))]
     return CrossValidation(Cs, folds, sols, labels)
+
+
+# ---------------------------------------------------------------- the optimizer's AUC gradient
+def auc_gradient_shape() -> dict:
+    """The GPU path's shape (sk_auc_gradient_shape): n_free <= lds_free keeps
+    the KKT matrix in LDS, more keeps it in a device scratch; max_free is the
+    most one problem may have; scratch_budget bytes are shared per launch."""
+    a, b, s = C.c_int32(), C.c_int32(), C.c_int64()
+    check(lib().sk_auc_gradient_shape(C.byref(a), C.byref(b), C.byref(s)))
+    return {"lds_free": a.value, "max_free": b.value, "scratch_budget": s.value}
+
+
+def auc_delta(dec, labels_of_test):
+    """(f, delta): the smoothed AUC of the decision values over the test
+    list's (positive, negative) pairs and its gradient with respect to them
+    (sk_auc_delta; compute_delta, optimizer/gradient.cpp:159-206).  A label
+    >= 0 counts as positive here.  One class only: f = 0, delta = 0."""
+    dec = np.ascontiguousarray(dec, dtype=np.float64).reshape(-1)
+    lab = np.ascontiguousarray(labels_of_test, dtype=np.float64).reshape(-1)
+    if len(dec) != len(lab):
+        raise ValueError("one label per decision value")
+    delta = np.zeros(max(len(dec), 1))
+    f = C.c_double()
+    check(lib().sk_auc_delta(dec.ctypes.data_as(_lib._F64P), lab.ctypes.data_as(_lib._F64P), len(dec),
+                             delta.ctypes.data_as(_lib._F64P), C.byref(f)))
+    return f.value, delta[:len(dec)]
+
+
+class AUCGradient:
+    """One problem's result: cg (d AUC / d C), fg[n_params] (d AUC / d kernel
+    parameter), d_u (the solution of solve_d's system, n_free + 1 entries;
+    empty when n_free is 0), n_free, n_bound, cg_iterations (products the
+    conjugate gradient formed) and finite (False when an output is inf/NaN)."""
+
+    def __init__(self, cg, fg, d_u, info):
+        self.cg, self.fg, self.d_u = float(cg), fg, d_u
+        self.n_free, self.n_bound = int(info.n_free), int(info.n_bound)
+        self.cg_iterations, self.finite = int(info.cg_iterations), bool(info.finite)
+
+    def __repr__(self):
+        return (f"AUCGradient(cg={self.cg:.6g}, fg={self.fg}, n_free={self.n_free}, n_bound={self.n_bound}, "
+                f"cg_iterations={self.cg_iterations}, finite={self.finite})")
+
+
+def _auc_problem(p):
+    if not isinstance(p, dict):
+        raise TypeError("a problem is a dict: train, test, C, alpha, rho, delta")
+    unknown = set(p) - {"train", "test", "C", "alpha", "rho", "delta"}
+    if unknown:
+        raise TypeError(f"unknown problem keys {sorted(unknown)}")
+    return (np.ascontiguousarray(p["train"], dtype=np.int32).reshape(-1),
+            np.ascontiguousarray(p["test"], dtype=np.int32).reshape(-1), float(p["C"]),
+            np.ascontiguousarray(p["alpha"], dtype=np.float64).reshape(-1), float(p["rho"]),
+            np.ascontiguousarray(p["delta"], dtype=np.float64).reshape(-1))
+
+
+def auc_gradient_batch(K, G, labels, problems: Sequence[dict], ctx=None, n_threads: int = 0):
+    """The gradient of the smoothed AUC of every problem's held-out examples
+    with respect to C and to each kernel parameter (sk_auc_gradient_batch;
+    steps 4 and 5 of GradientComputation::compute,
+    optimizer/gradient.cpp:107-156).  K is the Gram (n x n), G its derivative
+    matrices (n_params x n x n, or None), labels the n labels (none may be
+    0).  A problem is a dict with train, test (indices into K), C, alpha (the
+    trained fold's, in training order), rho and delta (auc_delta's, in test
+    order).  Returns one AUCGradient per problem.  ctx: a Context runs the
+    batch on its GPU; None runs it on n_threads host threads (0 = all).  Both
+    paths give the same bits."""
+    K = np.ascontiguousarray(K, dtype=np.float64)
+    if K.ndim != 2 or K.shape[0] != K.shape[1]:
+        raise ValueError("K must be a square matrix")
+    n = K.shape[0]
+    if G is None:
+        G = np.zeros((0, n, n))
+    G = np.ascontiguousarray(G, dtype=np.float64)
+    if G.ndim != 3 or G.shape[1:] != (n, n):
+        raise ValueError("G must be n_params matrices of K's shape")
+    n_params = G.shape[0]
+    labels = np.ascontiguousarray(labels, dtype=np.float64).reshape(-1)
+    if len(labels) != n:
+        raise ValueError("one label per row of K")
+    ps = [_auc_problem(p) for p in problems]
+    arr = (_lib.AucProblem * max(len(ps), 1))()
+    for a, (train, test, c, alpha, rho, delta) in zip(arr, ps):
+        if len(alpha) != len(train) or len(delta) != len(test):
+            raise ValueError("one alpha per training example and one delta per test example")
+        a.train, a.n_train = train.ctypes.data_as(_lib._I32P), len(train)
+        a.test, a.n_test = test.ctypes.data_as(_lib._I32P), len(test)
+        a.C, a.rho = c, rho
+        a.alpha, a.delta = alpha.ctypes.data_as(_lib._F64P), delta.ctypes.data_as(_lib._F64P)
+    doff = np.concatenate([[0], np.cumsum([len(p[0]) + 1 for p in ps])]).astype(np.int64)
+    cg = np.zeros(max(len(ps), 1))
+    fg = np.zeros((max(len(ps), 1), n_params))
+    du = np.zeros(max(int(doff[-1]), 1))
+    info = (_lib.AucInfo * max(len(ps), 1))()
+    head = (K.ctypes.data_as(_lib._F64P), G.ctypes.data_as(_lib._F64P) if n_params else None, n_params, n,
+            labels.ctypes.data_as(_lib._F64P), arr, len(ps))
+    outs = (cg.ctypes.data_as(_lib._F64P), fg.ctypes.data_as(_lib._F64P) if n_params else None,
+            du.ctypes.data_as(_lib._F64P), info)
+    if ctx is None:
+        check(lib().sk_auc_gradient_batch_host(*head, int(n_threads), *outs))
+    else:
+        check(lib().sk_auc_gradient_batch(ctx.handle, *head, *outs), ctx.handle)
+    res = []
+    for k in range(len(ps)):
+        nd = info[k].n_free + 1 if info[k].n_free > 0 else 0
+        res.append(AUCGradient(cg[k], fg[k].copy(), du[doff[k]:doff[k] + nd].copy(), info[k]))
+    return res
+
+
+def auc_objective(K, G, labels, n_folds: int, C: float, eps: float = 1e-3, max_iter: int = DEFAULT_MAX_ITER,
+                  ctx=None, n_threads: int = 0):
+    """One optimizer step's objective and gradient (Optimizer::optimize,
+    optimizer/optimizer.cpp:60-77): over the n_folds folds of cv_split, train
+    with C (svm_train_batch with each fold's test list), form auc_delta of
+    the held-out decision values and auc_gradient_batch, and sum f -= f0,
+    g[0] -= cg, g[1 + p] -= fg[p] in fold order.  Returns (f, g, records):
+    minus the summed smoothed AUC, its gradient with respect to (C,
+    parameters), and per fold a dict with f, delta, the SVMSolution and the
+    AUCGradient.  Training is without shrinking (see svm_train_batch)."""
+    labels = np.ascontiguousarray(labels, dtype=np.float64).reshape(-1)
+    n = len(labels)
+    if not 2 <= n_folds <= n:
+        raise ValueError("n_folds must be in [2, n]")
+    folds = [cv_split(n, n_folds, f) for f in range(n_folds)]
+    sols = svm_train_batch(K, labels, [dict(train=tr, test=ts, C=C, eps=eps, max_iter=max_iter)
+                                       for tr, ts in folds], ctx=ctx, n_threads=n_threads)
+    fd = [auc_delta(s.decision, labels[ts]) for s, (_, ts) in zip(sols, folds)]
+    grads = auc_gradient_batch(K, G, labels, [dict(train=tr, test=ts, C=C, alpha=s.alpha, rho=s.rho, delta=d)
+                                              for (tr, ts), s, (_, d) in zip(folds, sols, fd)],
+                               ctx=ctx, n_threads=n_threads)
+    n_params = 0 if G is None else len(G)
+    f, g = 0.0, np.zeros(1 + n_params)
+    records = []
+    for (f0, d), s, r in zip(fd, sols, grads):
+        f -= f0
+        g[0] -= r.cg
+        for p in range(n_params):
+            g[1 + p] -= r.fg[p]
+        records.append(dict(f=f0, delta=d, solution=s, gradient=r))
+    return f, g, records
+
+
+def optimize(objective, x0, bounds=None, **options):
+    """Minimise objective(x) -> (f, g) over x = (C, kernel parameters...) with
+    scipy.optimize.minimize(method="L-BFGS-B") and return its result.  bounds:
+    one (low, high) pair per entry of x (None = unbounded); C's lower bound is
+    raised to 1e-5, the one the reference sets (optimizer/optimizer.cpp:29).
+    This stands in for the reference's f2c lbfgsb.c, which is neither restated
+    nor pinned: the iterates are SciPy's, not the reference's.  SciPy is
+    imported here, so the package does not depend on it."""
+    from scipy.optimize import minimize
+    x0 = np.asarray(x0, dtype=np.float64).reshape(-1)
+    bounds = [(None, None)] * len(x0) if bounds is None else [tuple(b) for b in bounds]
+    if len(bounds) != len(x0):
+        raise ValueError("one (low, high) pair per entry of x0")
+    lo, hi = bounds[0]
+    bounds[0] = (1e-5 if lo is None else max(1e-5, lo), hi)
+
+    def fun(x):
+        f, g = objective(x)[:2]
+        return float(f), np.asarray(g, dtype=np.float64)
+
+    return minimize(fun, x0, jac=True, method="L-BFGS-B", bounds=bounds, options=options or None)

@@ -1,0 +1,2 @@
+// Stand-in for <boost/numeric/ublas/io.hpp>: the reference includes it and uses
+// nothing from it in the code that is compiled.  TEST INFRASTRUCTURE ONLY.
