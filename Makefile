@@ -17,7 +17,8 @@ HOST_SRC := $(ROOT)stem_kernel_amd/csrc/host/synth.cpp $(ROOT)stem_kernel_amd/cs
             $(ROOT)stem_kernel_amd/csrc/host/readers.cpp $(ROOT)stem_kernel_amd/csrc/host/shard.cpp \
             $(ROOT)stem_kernel_amd/csrc/host/svm_predict.cpp $(ROOT)stem_kernel_amd/csrc/host/fold_host.cpp \
             $(ROOT)stem_kernel_amd/csrc/host/svm_train.cpp $(ROOT)stem_kernel_amd/csrc/host/auc_gradient.cpp
-API_SRC := $(ROOT)stem_kernel_amd/csrc/sk_api.cpp
+# the host runtime behind the ABI (they share host/runtime.h, host/runtime_types.h)
+API_SRC := $(ROOT)stem_kernel_amd/csrc/sk_api.cpp $(ROOT)stem_kernel_amd/csrc/host/pairs_dag.cpp
 HIP_SRC := $(ROOT)stem_kernel_amd/csrc/kernels/dag_stem.hip $(ROOT)stem_kernel_amd/csrc/kernels/profile_string.hip \
            $(ROOT)stem_kernel_amd/csrc/kernels/bpla.hip $(ROOT)stem_kernel_amd/csrc/kernels/stem4d.hip \
            $(ROOT)stem_kernel_amd/csrc/kernels/phmm.hip $(ROOT)stem_kernel_amd/csrc/kernels/bpla_grad.hip \
@@ -75,27 +76,38 @@ clean:
 
 .PHONY: all lib cli oracle clean
 
-# The diagnostic and experiment builds below recompile one or two sources with
+# The diagnostic and experiment builds below recompile some sources with
 # extra defines and link them with the default build's other objects (make lib
 # first): $(call relink,out.so,replaced default objects,their replacements)
 relink = $(LINK) -o $(1) $(filter-out $(2),$(HOST_OBJ) $(HIP_OBJ)) $(3) $(LINK_LIBS)
+# the default objects of the host runtime (API_SRC), and the same set under a build directory
+API_OBJ := $(patsubst $(ROOT)stem_kernel_amd/csrc/%.cpp,$(BUILD)/%.o,$(API_SRC))
+api_obj = $(patsubst $(BUILD)/%.o,$(1)/%.o,$(API_OBJ))
 
 # diagnostic build with in-kernel phase stamps (never the shipped library)
 STAMPS_LIB := $(ROOT)build/libstem_kernel_amd_stamps.so
-stamps:
-	@mkdir -p $(BUILD)/stamps
+$(BUILD)/stamps/%.o: $(ROOT)stem_kernel_amd/csrc/%.cpp $(HDRS)
+	@mkdir -p $(dir $@)
+	$(HIPCC) $(CXXFLAGS) -DSK_STAMPS -D__HIP_PLATFORM_AMD__ -c $< -o $@
+stamps: $(call api_obj,$(BUILD)/stamps)
 	$(HIPCC) $(HIPFLAGS) -DSK_STAMPS -x hip -c $(ROOT)stem_kernel_amd/csrc/kernels/dag_stem.hip -o $(BUILD)/stamps/dag_stem.o
-	$(HIPCC) $(CXXFLAGS) -DSK_STAMPS -D__HIP_PLATFORM_AMD__ -c $(API_SRC) -o $(BUILD)/stamps/sk_api.o
-	$(call relink,$(STAMPS_LIB),$(BUILD)/sk_api.o $(BUILD)/kernels/dag_stem.o,$(BUILD)/stamps/sk_api.o $(BUILD)/stamps/dag_stem.o)
+	$(call relink,$(STAMPS_LIB),$(API_OBJ) $(BUILD)/kernels/dag_stem.o,$(call api_obj,$(BUILD)/stamps) $(BUILD)/stamps/dag_stem.o)
 .PHONY: stamps
 
 # experiment build: make variant NAME=x DEFS="-DSK_PW=3 [-DSK_STAMPS]" -> build/libsk_x.so
-variant:
-	@mkdir -p $(BUILD)/var/$(NAME)
+# (the objects of a NAME are rebuilt on every call, FORCE: another DEFS may go
+# by the same NAME, where the stamps objects have one set of defines and
+# follow their sources like the default build's)
+ifneq ($(NAME),)
+$(BUILD)/var/$(NAME)/%.o: $(ROOT)stem_kernel_amd/csrc/%.cpp $(HDRS) FORCE
+	@mkdir -p $(dir $@)
+	$(HIPCC) $(CXXFLAGS) $(DEFS) -D__HIP_PLATFORM_AMD__ -c $< -o $@
+endif
+variant: $(call api_obj,$(BUILD)/var/$(NAME))
 	$(HIPCC) $(HIPFLAGS) $(DEFS) -x hip -c $(ROOT)stem_kernel_amd/csrc/kernels/dag_stem.hip -o $(BUILD)/var/$(NAME)/dag_stem.o
-	$(HIPCC) $(CXXFLAGS) $(DEFS) -D__HIP_PLATFORM_AMD__ -c $(API_SRC) -o $(BUILD)/var/$(NAME)/sk_api.o
-	$(call relink,$(BUILD)/libsk_$(NAME).so,$(BUILD)/sk_api.o $(BUILD)/kernels/dag_stem.o,$(BUILD)/var/$(NAME)/sk_api.o $(BUILD)/var/$(NAME)/dag_stem.o)
-.PHONY: variant
+	$(call relink,$(BUILD)/libsk_$(NAME).so,$(API_OBJ) $(BUILD)/kernels/dag_stem.o,$(call api_obj,$(BUILD)/var/$(NAME)) $(BUILD)/var/$(NAME)/dag_stem.o)
+FORCE:
+.PHONY: variant FORCE
 
 # fold kernel experiment build: make variantf NAME=x DEFS="-DSK_FOLD_TIMING" -> build/libsk_x.so
 variantf:

@@ -24,6 +24,7 @@
 #include <thread>
 #include <vector>
 
+#include "host/runtime.h"
 #include "host/sk_internal.h"
 #include "stem_kernel.h"
 
@@ -89,12 +90,6 @@ void parallel_rows(int64_t n, F f, bool lower = false) {
 }  // namespace
 
 namespace sk {
-// accessors into the context (sk_api.cpp)
-hipStream_t ctx_stream(sk_context* ctx);
-int ctx_device(sk_context* ctx);
-void*& ctx_comm(sk_context* ctx);
-int ctx_fail(sk_context* ctx, int code, const std::string& msg);
-
 // What sk_comm_init leaves in the context: the communicator and the device
 // status word of sk_gram_sharded's agreement, allocated together so that a
 // sharded Gram has no failure point before its first collective.

@@ -42,16 +42,9 @@
 #include <vector>
 
 #include "../host/auc_gradient.h"
+#include "../host/runtime.h"
 
-struct sk_context;
 namespace sk {
-hipStream_t ctx_stream(sk_context* ctx);
-int ctx_device(sk_context* ctx);
-int ctx_fail(sk_context* ctx, int code, const std::string& msg);
-hipError_t call_begin(sk_context* ctx);
-hipError_t lev_mark(sk_context* ctx, hipStream_t s);
-hipError_t lev_collect(sk_context* ctx);
-void lev_reset(sk_context* ctx);
 
 namespace {
 

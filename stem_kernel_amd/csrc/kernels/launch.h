@@ -1,4 +1,5 @@
-// Launch descriptors shared by the host runtime (sk_api.cpp) and the kernels.
+// Launch descriptors shared by the host runtime (sk_api.cpp, host/pairs_dag.cpp)
+// and the kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -413,7 +414,7 @@ size_t stem_lds_bytes(const StemLaunch& P, int nwaves);
 hipError_t launch_stem(const StemLaunch& P, int grid, int nwaves, hipStream_t st);
 // the launch's shared Gamma tables (P.gam_shared): P.n_slots workgroups of the
 // stem kernel's shape, on a stream the stem launch that reads them is ordered
-// behind (sk_api.cpp: all classes' tables first, ahead of the stem launches
+// behind (host/pairs_dag.cpp: all classes' tables first, ahead of the stem launches
 // and of the string kernel's side stream)
 hipError_t launch_gamma_tables(const StemLaunch& P, int nwaves, hipStream_t st);
 hipError_t stem_kernel_attr(int max_nl, int* max_dyn_lds, int* vgprs, int* max_waves);

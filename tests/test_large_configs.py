@@ -60,7 +60,7 @@ def _expected(name, kind):
 
 
 def _maxk(nl):
-    # sk_api.cpp in_class = dag_stem.hip stem_maxk(nl + 1): 64-node slots per
+    # host/pairs_dag.cpp in_class = dag_stem.hip stem_maxk(nl + 1): 64-node slots per
     # lane for the y's nodes plus one free slot (the sweep's dummy target),
     # rounded up to a multiple of 4 -- except 17 slots (1,024-1,087 nodes), a
     # class of its own

@@ -1,10 +1,11 @@
 """The dataset packing (sk_api.cpp pack_dataset) runs its per-example passes
 on host threads and appends at prefix offsets: the packed arrays must not
-depend on the thread count.  tools/pack_compare.cpp includes the library
-source and hashes every packed array (the y-role records, every SK_BIG x-role
-array, the per-example ex_* vectors and key tables); it is built here (host
-code only) and run with one thread and with eight (SK_PACK_THREADS), and both
-must equal GOLDEN: the hashes of the serial packer before the threaded one
+depend on the thread count.  tools/pack_compare.cpp calls the library's
+sk::pack_dataset (host/runtime_types.h) and hashes every packed array (the
+y-role records, every SK_BIG x-role array, the per-example ex_* vectors and
+key tables); it is built here (host code only, at -O1: the packer it runs is
+the library's, built as shipped) and run with one thread and with eight
+(SK_PACK_THREADS), and both must equal GOLDEN: the hashes of the serial packer before the threaded one
 (commit 61ba1f6^, built in a worktree with this pack_compare.cpp, r05), so a
 rebase bug that does not depend on the thread count fails here too."""
 import os
@@ -18,10 +19,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 @pytest.fixture(scope="module")
 def pack_compare(tmp_path_factory):
     exe = str(tmp_path_factory.mktemp("pc") / "pack_compare")
-    src = os.path.join(ROOT, "stem_kernel_amd", "csrc", "sk_api.cpp")
     lib = os.path.join(ROOT, "stem_kernel_amd")
     subprocess.run(["/opt/rocm/bin/hipcc", "-O1", "-std=c++17", "-I", os.path.join(ROOT, "include"), "-I",
-                    os.path.join(ROOT, "stem_kernel_amd", "csrc"), "-D__HIP_PLATFORM_AMD__", f'-DSRC="{src}"',
+                    os.path.join(ROOT, "stem_kernel_amd", "csrc"), "-D__HIP_PLATFORM_AMD__",
                     os.path.join(ROOT, "tools", "pack_compare.cpp"), "-o", exe, "-L", lib, "-lstem_kernel_amd",
                     f"-Wl,-rpath,{lib}", "-L/opt/rocm/lib", "-lrccl"], check=True, timeout=600)
     return exe

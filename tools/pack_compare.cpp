@@ -1,11 +1,24 @@
-// Host packing check (CPU only): build with two versions of sk_api.cpp and
-// compare the hashes of the packed arrays and the pack time, e.g.
-//   git show HEAD~1:stem_kernel_amd/csrc/sk_api.cpp > /tmp/old.cpp
-//   hipcc -O3 -std=c++17 -Iinclude -Istem_kernel_amd/csrc -D__HIP_PLATFORM_AMD__ '-DSRC="/tmp/old.cpp"' \
-//     tools/pack_compare.cpp -o /tmp/pc_old -Lstem_kernel_amd -lstem_kernel_amd -Wl,-rpath,$PWD/stem_kernel_amd -L/opt/rocm/lib -lrccl
-//   /tmp/pc_old 2048 200   (likewise with -DSRC=... the tree's sk_api.cpp)
-#include SRC
+// Host packing check (CPU only): packs a synthetic dataset with the
+// sk::pack_dataset of the library it links (sk_api.cpp) and prints the
+// hashes of the packed arrays and the pack time.  To compare two versions,
+// build each version's own tools/pack_compare.cpp in its tree against that
+// tree's library (make lib) and run both, e.g.
+//   git worktree add /tmp/old OLD && make -C /tmp/old lib
+//   (cd /tmp/old && hipcc -O3 -std=c++17 -Iinclude -Istem_kernel_amd/csrc -D__HIP_PLATFORM_AMD__ \
+//     tools/pack_compare.cpp -o /tmp/pc_old -Lstem_kernel_amd -lstem_kernel_amd -Wl,-rpath,$PWD/stem_kernel_amd \
+//     -L/opt/rocm/lib -lrccl)
+//   /tmp/pc_old 2048 200   (likewise in this tree; the pack time is the library's, at its own -O3)
+// An OLD from before host/runtime_types.h has the tool that includes the
+// library source instead: add '-DSRC="/tmp/old/stem_kernel_amd/csrc/sk_api.cpp"'
+// to its line, as its own header says.
 #include <chrono>
+#include <cstdio>
+#include <cstdlib>
+
+#include "host/runtime_types.h"
+
+using sk::HostPack;
+using sk::pack_dataset;
 template <class V> static uint64_t hv(const V& v, uint64_t h) {
   typedef typename V::value_type T;
   const unsigned char* p = reinterpret_cast<const unsigned char*>(v.data());
