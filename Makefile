@@ -16,7 +16,8 @@ LINK_LIBS := -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
 HOST_SRC := $(ROOT)stem_kernel_amd/csrc/host/synth.cpp $(ROOT)stem_kernel_amd/csrc/host/example_build.cpp \
             $(ROOT)stem_kernel_amd/csrc/host/readers.cpp $(ROOT)stem_kernel_amd/csrc/host/shard.cpp \
             $(ROOT)stem_kernel_amd/csrc/host/svm_predict.cpp $(ROOT)stem_kernel_amd/csrc/host/fold_host.cpp \
-            $(ROOT)stem_kernel_amd/csrc/host/svm_train.cpp $(ROOT)stem_kernel_amd/csrc/host/auc_gradient.cpp
+            $(ROOT)stem_kernel_amd/csrc/host/svm_train.cpp $(ROOT)stem_kernel_amd/csrc/host/auc_gradient.cpp \
+            $(ROOT)stem_kernel_amd/csrc/host/feature_gram.cpp
 # the host runtime behind the ABI (they share host/runtime.h, host/runtime_types.h)
 API_SRC := $(ROOT)stem_kernel_amd/csrc/sk_api.cpp $(ROOT)stem_kernel_amd/csrc/host/pairs_dag.cpp
 HIP_SRC := $(ROOT)stem_kernel_amd/csrc/kernels/dag_stem.hip $(ROOT)stem_kernel_amd/csrc/kernels/profile_string.hip \
@@ -25,7 +26,8 @@ HIP_SRC := $(ROOT)stem_kernel_amd/csrc/kernels/dag_stem.hip $(ROOT)stem_kernel_a
            $(ROOT)stem_kernel_amd/csrc/kernels/dag_stem_big.hip $(ROOT)stem_kernel_amd/csrc/kernels/fold.hip \
            $(ROOT)stem_kernel_amd/csrc/kernels/fold_sample.hip $(ROOT)stem_kernel_amd/csrc/kernels/fold_ali.hip \
            $(ROOT)stem_kernel_amd/csrc/kernels/la_protein.hip $(ROOT)stem_kernel_amd/csrc/kernels/simpal.hip \
-           $(ROOT)stem_kernel_amd/csrc/kernels/svm_smo.hip $(ROOT)stem_kernel_amd/csrc/kernels/auc_grad.hip
+           $(ROOT)stem_kernel_amd/csrc/kernels/svm_smo.hip $(ROOT)stem_kernel_amd/csrc/kernels/auc_grad.hip \
+           $(ROOT)stem_kernel_amd/csrc/kernels/feature_gram.hip
 HDRS := $(wildcard $(ROOT)stem_kernel_amd/csrc/*/*.h) $(ROOT)include/stem_kernel.h $(ROOT)stem_kernel_amd/csrc/ribosum85_60.inc \
         $(ROOT)stem_kernel_amd/csrc/blosum62.inc
 
@@ -63,6 +65,9 @@ $(BUILD)/kernels/svm_smo.o: HIPFLAGS += -ffp-contract=off
 # the AUC gradient's conjugate gradient amplifies rounding: both paths round every operation alone
 $(BUILD)/host/auc_gradient.o: CXXFLAGS += -ffp-contract=off
 $(BUILD)/kernels/auc_grad.o: HIPFLAGS += -ffp-contract=off
+# the feature-vector dot is libsvm's sparse merge bit for bit: multiply, then add, on both paths
+$(BUILD)/host/feature_gram.o: CXXFLAGS += -ffp-contract=off
+$(BUILD)/kernels/feature_gram.o: HIPFLAGS += -ffp-contract=off
 
 $(LIB): $(HOST_OBJ) $(HIP_OBJ)
 	$(LINK) -o $@ $^ $(LINK_LIBS)
@@ -135,6 +140,7 @@ $(BUILD)/exp/%.o: $(ROOT)stem_kernel_amd/csrc/%.cpp $(HDRS)
 $(BUILD)/exp/host/synth.o: CXXFLAGS += -ffp-contract=off
 $(BUILD)/exp/host/svm_train.o: CXXFLAGS += -ffp-contract=off
 $(BUILD)/exp/host/auc_gradient.o: CXXFLAGS += -ffp-contract=off
+$(BUILD)/exp/host/feature_gram.o: CXXFLAGS += -ffp-contract=off
 $(EXP_LIB): $(EXP_OBJ) $(HIP_OBJ)
 	$(LINK) -o $@ $^ $(LINK_LIBS)
 .PHONY: exp

@@ -716,6 +716,88 @@ int sk_auc_gradient_batch_host(const double *gram, const double *grads, int32_t 
  * problem may have; the problems of one launch share *scratch_budget bytes. */
 int sk_auc_gradient_shape(int32_t *lds_free, int32_t *max_free, int64_t *scratch_budget);
 
+/* ---------------------------------------------------------------- feature-vector Grams */
+/* The reference's rbf_optimizer, poly_optimizer and sigmoid_optimizer
+ * (Optimizer<RBFKernel|PolyKernel|SigmoidKernel, GradientComputationAUC>) read
+ * a libsvm feature file and need a Gram K and its derivative matrices
+ * dK/dparam at every step (CM::calculate_matrix, optimizer/rbf_kernel.cpp,
+ * poly_kernel.cpp, sigmoid_kernel.cpp).  With d = dot(x, y), libsvm's sparse
+ * merge (sum = 0; sum += x.value * y.value over the shared indices in
+ * ascending order; multiply and add rounded separately):
+ *   SK_FEAT_RBF      params (gamma):        w = dot(x,x) + dot(y,y) - 2 d;
+ *                    K = exp(-gamma w); G0 = -w exp(-gamma w)
+ *   SK_FEAT_POLY     params (gamma, coef0), integer degree: t = gamma d + coef0;
+ *                    K = powi(t, degree); v = powi(t, degree - 1) degree;
+ *                    G0 = v d; G1 = v   (powi: libsvm's square-and-multiply)
+ *   SK_FEAT_SIGMOID  params (gamma, coef0): t = gamma d + coef0; K = tanh(t);
+ *                    w = cosh(t); v = 1 / (w w); G0 = v d; G1 = v
+ * The dot matrix is the reference's bit for bit on both paths; so is the whole
+ * polynomial kernel; exp / tanh / cosh are libm's on the host path and the
+ * device library's on the GPU (within the project's 1e-6 relative bound;
+ * DESIGN.md 17 has the measured deviation in ulps). */
+typedef struct sk_features sk_features;
+typedef enum sk_feature_kernel { SK_FEAT_RBF = 0, SK_FEAT_POLY = 1, SK_FEAT_SIGMOID = 2 } sk_feature_kernel;
+/* A feature set from CSR arrays: example i holds index[row_ptr[i] ..
+ * row_ptr[i+1]) with their values; row_ptr[0] = 0; labels may be NULL (all
+ * 0).  The arrays are copied.  SK_ERR_INVALID for an index < 0, indices not
+ * strictly ascending within an example, or a value that is not finite
+ * (message: sk_features_last_error). */
+int sk_features_create(int32_t n, const int64_t *row_ptr, const int32_t *index, const double *value,
+                       const int32_t *labels, sk_features **out);
+/* From libsvm text, as the reference's read_data reads it
+ * (optimizer/rbf_kernel.cpp:69-104): one example per line, the label atoi of
+ * the first token, every further token index:value; a blank line is an example
+ * with label 0 and no features.  Stricter than read_data, whose terminator is
+ * index -1 and which does not check its sscanf: a token without ':', an index
+ * that is not an integer or is < 0, indices not strictly ascending within a
+ * line, a value that is not a number or not finite are SK_ERR_INVALID, with a
+ * message that begins "line N:". */
+int sk_features_parse(const char *text, size_t len, sk_features **out);
+int sk_features_read(const char *path, sk_features **out);
+/* Also drops the dot matrices any context keeps resident for the set. */
+int sk_features_free(sk_features *fs);
+/* *n examples, *d used columns (distinct indices), *nnz stored entries. */
+int sk_features_shape(const sk_features *fs, int32_t *n, int32_t *d, int64_t *nnz);
+int sk_features_labels(const sk_features *fs, int32_t *out);
+/* The examples back as CSR: row_ptr n + 1, index and value nnz entries (each
+ * may be NULL). */
+int sk_features_rows(const sk_features *fs, int64_t *row_ptr, int32_t *index, double *value);
+/* The last error of an sk_features_* or sk_feature_*_host call on this thread. */
+const char *sk_features_last_error(void);
+/* The GPU path's shape and the limits of both paths: the dot kernel computes
+ * *tile x *tile outputs per workgroup in k-slices of *k_slice columns.  A set
+ * may hold at most *max_n examples (16,384: the resident dot matrix, K and two
+ * gradient matrices are 4 n^2 doubles on the device, 8 GiB), and the examples
+ * of a call (both sets of a cross call) times the used columns (of their
+ * union) at most *max_dense entries (2^28: the examples are stored dense over
+ * the compacted columns, 2 GiB).  Over a limit: SK_ERR_UNSUPPORTED before
+ * anything is launched, with the limit named in the message. */
+int sk_feature_gram_shape(int32_t *tile, int32_t *k_slice, int32_t *max_n, int64_t *max_dense);
+/* The dot matrix D[i][j] = dot(xs_i, ys_j) (ys NULL: xs with itself, n x n;
+ * otherwise n_xs x n_ys over the union of both sets' columns), downloaded.
+ * The context computes D on the first call for the set (or the pair) and
+ * keeps it resident on its device until the set is freed or the context is
+ * closed (the four most recent per context); the calls below use the same D,
+ * so a call with new parameters launches only the epilogue kernel
+ * (sk_last_launch_ms counts every kernel launched). */
+int sk_feature_dots(sk_context *ctx, const sk_features *xs, const sk_features *ys, double *out);
+int sk_feature_dots_host(const sk_features *xs, const sk_features *ys, int32_t n_threads, double *out);
+/* K (n x n) and, unless out_g is NULL, the derivative matrices G[P][n][n] (P =
+ * 1 for RBF, 2 otherwise: the layout sk_auc_gradient_batch takes), exactly
+ * symmetric.  degree is read for SK_FEAT_POLY only (>= 0). */
+int sk_feature_gram(sk_context *ctx, const sk_features *xs, int32_t kind, int32_t degree, const double *params,
+                    double *out_k, double *out_g);
+/* The same on n_threads host threads (0 = hardware concurrency) with libm:
+ * what the GPU path is compared with. */
+int sk_feature_gram_host(const sk_features *xs, int32_t kind, int32_t degree, const double *params,
+                         int32_t n_threads, double *out_k, double *out_g);
+/* The rectangular K(test, train), n_test x n_train, for predicting with a
+ * model trained at the optimum. */
+int sk_feature_gram_cross(sk_context *ctx, const sk_features *test, const sk_features *train, int32_t kind,
+                          int32_t degree, const double *params, double *out_k);
+int sk_feature_gram_cross_host(const sk_features *test, const sk_features *train, int32_t kind, int32_t degree,
+                               const double *params, int32_t n_threads, double *out_k);
+
 /* ---------------------------------------------------------------- diagnostics */
 /* Milliseconds spent in the last compute call's dominant kernel (DAG stem
  * DP), measured with HIP events on the context's stream, and its launch

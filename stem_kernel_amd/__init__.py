@@ -14,4 +14,9 @@ from .svm import (  # noqa: F401
     svm_train_shape,
 )
 
+from .features import (  # noqa: F401
+    FeatureSet, PolyKernel, RBFKernel, SigmoidKernel, feature_auc_objective, feature_dots, feature_gram,
+    feature_gram_cross, feature_gram_shape, optimize_features,
+)
+
 __version__ = "0.1.0"

@@ -69,6 +69,7 @@ _I32P = C.POINTER(C.c_int32)
 _U32P = C.POINTER(C.c_uint32)
 _F32P = C.POINTER(C.c_float)
 _F64P = C.POINTER(C.c_double)
+_I64P = C.POINTER(C.c_int64)
 
 # name -> (restype, argtypes); every symbol include/stem_kernel.h declares
 SIGNATURES = {
@@ -187,6 +188,21 @@ SIGNATURES = {
     "sk_auc_gradient_batch_host": (C.c_int, [_F64P, _F64P, C.c_int32, C.c_int32, _F64P, C.POINTER(AucProblem),
                                              C.c_int32, C.c_int32, _F64P, _F64P, _F64P, C.POINTER(AucInfo)]),
     "sk_auc_gradient_shape": (C.c_int, [_I32P, _I32P, C.POINTER(C.c_int64)]),
+    "sk_features_create": (C.c_int, [C.c_int32, _I64P, _I32P, _F64P, _I32P, C.POINTER(_P)]),
+    "sk_features_parse": (C.c_int, [C.c_char_p, C.c_size_t, C.POINTER(_P)]),
+    "sk_features_read": (C.c_int, [C.c_char_p, C.POINTER(_P)]),
+    "sk_features_free": (C.c_int, [_P]),
+    "sk_features_shape": (C.c_int, [_P, _I32P, _I32P, _I64P]),
+    "sk_features_labels": (C.c_int, [_P, _I32P]),
+    "sk_features_rows": (C.c_int, [_P, _I64P, _I32P, _F64P]),
+    "sk_features_last_error": (C.c_char_p, []),
+    "sk_feature_gram_shape": (C.c_int, [_I32P, _I32P, _I32P, _I64P]),
+    "sk_feature_dots": (C.c_int, [_P, _P, _P, _F64P]),
+    "sk_feature_dots_host": (C.c_int, [_P, _P, C.c_int32, _F64P]),
+    "sk_feature_gram": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _F64P, _F64P, _F64P]),
+    "sk_feature_gram_host": (C.c_int, [_P, C.c_int32, C.c_int32, _F64P, C.c_int32, _F64P, _F64P]),
+    "sk_feature_gram_cross": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _F64P, _F64P]),
+    "sk_feature_gram_cross_host": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _F64P, C.c_int32, _F64P]),
 }
 
 _lock = threading.Lock()

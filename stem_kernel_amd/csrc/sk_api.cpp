@@ -34,6 +34,7 @@
 #include "kernels/fold_rng.h"
 #include "host/sk_internal.h"
 #include "host/runtime_types.h"
+#include "host/feature_gram.h"
 #include "kernels/device_set.h"
 #include "kernels/launch.h"
 #include "ribosum85_60.inc"
@@ -2982,6 +2983,7 @@ int sk_close(sk_context* ctx) {
   // buffers they read are freed
   for (hipStream_t st : {ctx->stream, ctx->side, ctx->cls, ctx->aux, ctx->cps})
     if (st) (void)hipStreamSynchronize(st);
+  sk::feat_dots_forget(ctx, nullptr);  // the feature-vector Grams' resident dot matrices
   sk::comm_destroy(ctx->comm);
   ctx->comm = nullptr;
   if (ctx->scratch) (void)hipFree(ctx->scratch);

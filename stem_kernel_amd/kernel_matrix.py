@@ -796,6 +796,14 @@ class Context:
         return svm.auc_objective(K, G, labels, n_folds, C, eps=eps, ctx=self,
                                  max_iter=svm.DEFAULT_MAX_ITER if max_iter is None else max_iter)
 
+    def feature_auc_objective(self, fs, kernel, n_folds: int, C: float, eps: float = 1e-3, max_iter=None):
+        """One step of the rbf / poly / sigmoid optimizer on this GPU:
+        features.feature_gram, then svm.auc_objective over it
+        (optimizer/optimizer.cpp:45-77).  Returns (f, g, records) with g over
+        (C, the kernel's parameters)."""
+        from . import features
+        return features.feature_auc_objective(fs, kernel, n_folds, C, eps=eps, max_iter=max_iter, ctx=self)
+
     def comm_init(self, uid: bytes, rank: int, world: int) -> None:
         """This context's RCCL communicator (sk_comm_init); uid = the 128
         bytes rank 0 drew with sk_comm_unique_id (see shard.rccl_init)."""
