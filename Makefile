@@ -19,7 +19,9 @@ HOST_SRC := $(ROOT)stem_kernel_amd/csrc/host/synth.cpp $(ROOT)stem_kernel_amd/cs
             $(ROOT)stem_kernel_amd/csrc/host/svm_train.cpp $(ROOT)stem_kernel_amd/csrc/host/auc_gradient.cpp \
             $(ROOT)stem_kernel_amd/csrc/host/feature_gram.cpp
 # the host runtime behind the ABI (they share host/runtime.h, host/runtime_types.h)
-API_SRC := $(ROOT)stem_kernel_amd/csrc/sk_api.cpp $(ROOT)stem_kernel_amd/csrc/host/pairs_dag.cpp
+API_SRC := $(ROOT)stem_kernel_amd/csrc/sk_api.cpp $(addprefix $(ROOT)stem_kernel_amd/csrc/host/,context.cpp pack.cpp \
+           dataset.cpp dataset_io.cpp fold_gpu.cpp pairs_dag.cpp pairs_bpla.cpp pairs_la_protein.cpp \
+           pairs_simpal.cpp pairs_stem4d.cpp)
 HIP_SRC := $(ROOT)stem_kernel_amd/csrc/kernels/dag_stem.hip $(ROOT)stem_kernel_amd/csrc/kernels/profile_string.hip \
            $(ROOT)stem_kernel_amd/csrc/kernels/bpla.hip $(ROOT)stem_kernel_amd/csrc/kernels/stem4d.hip \
            $(ROOT)stem_kernel_amd/csrc/kernels/phmm.hip $(ROOT)stem_kernel_amd/csrc/kernels/bpla_grad.hip \

@@ -1,5 +1,5 @@
 // Host pieces of the GPU folds (the batch driver, which needs the context,
-// is in sk_api.cpp): the Boltzmann tables, the nucleotide codes, the
+// is in host/fold_gpu.cpp): the Boltzmann tables, the nucleotide codes, the
 // --noLonelyPairs pair filters and the batch plan.  No GPU call in here.
 #pragma once
 

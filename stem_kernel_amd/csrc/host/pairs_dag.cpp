@@ -155,16 +155,6 @@ int plan_stem_items(sk_context* ctx, const HostPack& PX, const HostPack& PY, con
       }
     }
     if (best == 0) return fail(ctx, SK_ERR_UNSUPPORTED, "y example too large for LDS");
-#ifdef SK_STAMPS
-    // diagnostics: SK_FORCE_WAVES=w,p -> w waves per workgroup, p workgroups per CU
-    if (const char* fw = SK_KNOB("SK_FORCE_WAVES")) {
-      int w = 0, pc = 0;
-      if (std::sscanf(fw, "%d,%d", &w, &pc) == 2 && w >= 1 && w <= C.nwaves && pc >= 1) {
-        C.nwaves = w;
-        per_cu = pc;
-      }
-    }
-#endif
     C.grid = ctx->n_cu * per_cu;
     // Work items = pairs of one y (the workgroup stages one y DAG in LDS
     // and waits for its slowest wave at every item boundary, about half a

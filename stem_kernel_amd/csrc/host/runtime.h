@@ -1,6 +1,6 @@
 // The host runtime's call API (not part of the ABI): what a compute call of
 // any subsystem uses of a context -- the planners, the SMO and AUC-gradient
-// hosts beside their kernels, the sharded Gram.  Defined in sk_api.cpp
+// hosts beside their kernels, the sharded Gram.  Defined in host/context.cpp
 // (comm_destroy: host/shard.cpp); the structs behind the
 // handles are in host/runtime_types.h.
 #pragma once

@@ -1,6 +1,6 @@
 // Internals of the host runtime (not part of the ABI): the dataset and
 // context structs behind the C handles, the packed host image, the helpers
-// sk_api.cpp and the planners under host/ share, and the entry functions
+// sk_api.cpp and the subsystems under host/ share, and the entry functions
 // they call across files.  Host code only.
 #pragma once
 
@@ -422,10 +422,40 @@ struct Arena {
 };
 
 // ------------------------------------------------------------ across files
-// the packer (sk_api.cpp; tools/pack_compare.cpp times it)
+// the packer (host/pack.cpp; tools/pack_compare.cpp times it) and one
+// position's BPLA weights as it forms them (sk_dataset_bpla_weights)
 int pack_dataset(sk_dataset* ds, std::string& err, const std::function<void()>* after_x = nullptr);
-// the DAG stem and string planner behind sk_api.cpp's run_pairs (host/pairs_dag.cpp)
+float4 bpla_weight(const Example& X, int i);
+// the planners behind sk_api.cpp's run_pairs, one per family of kinds: the
+// DAG stem and string kinds (host/pairs_dag.cpp), BPLA (host/pairs_bpla.cpp),
+// protein LA (host/pairs_la_protein.cpp), palindromes (host/pairs_simpal.cpp)
+// and the 4-D stem kernel (host/pairs_stem4d.cpp)
 int run_dag_pairs(sk_context* ctx, sk_dataset* xs_, sk_dataset* ys_, const sk_kernel_params* kp,
                   const int32_t* x, const int32_t* y, int64_t n, double* out_dev);
+int run_bpla(sk_context* ctx, sk_dataset* xs_, sk_dataset* ys_, const sk_kernel_params* kp,
+             const int32_t* x, const int32_t* y, int64_t n, double* out_dev);
+int run_la_protein(sk_context* ctx, sk_dataset* xs_, sk_dataset* ys_, const sk_kernel_params* kp,
+                   const int32_t* x, const int32_t* y, int64_t n, double* out_dev);
+int run_simpal(sk_context* ctx, sk_dataset* xs_, sk_dataset* ys_, const sk_kernel_params* kp,
+               const int32_t* x, const int32_t* y, int64_t n, double* out_dev);
+int run_stem4d(sk_context* ctx, sk_dataset* xs_, sk_dataset* ys_, const sk_kernel_params* kp,
+               const int32_t* x, const int32_t* y, int64_t n, double* out_dev);
+// the BPLA gradient driver behind sk_bpla_gradients (host/pairs_bpla.cpp)
+int bpla_gradients(sk_context* ctx, sk_dataset* xs_, sk_dataset* ys_, const sk_kernel_params* kp,
+                   const int32_t* x, const int32_t* y, int64_t n, double* value, double* grad);
+// example builders of host/dataset.cpp that the GPU folds' adders
+// (host/fold_gpu.cpp), the byte format (host/dataset_io.cpp) and sk_api.cpp
+// use.  kAaMaxRows: protein examples of this many rows or more are refused
+// (below it every float product and sum of LAScore's weight n is an exact
+// integer, < 2^24)
+constexpr int kAaMaxRows = 4096;
+int char2aa(int c);
+int pal_args(size_t n, int32_t seed_length, int32_t min_loop, int32_t max_dist, std::string* err);
+void build_palindromes(Example& ex, const std::string& seq, const double* bpp, int32_t s, int32_t min_loop,
+                       int32_t max_dist);
+std::string lower(const char* s);
+int add_examples_threaded(sk_dataset* ds, int32_t n, int32_t n_rows, const char* const* rows,
+                          const double* const* bpp_rows, const char* const* labels, float th,
+                          int use_bp, int32_t n_threads, bool consensus = false);
 
 }  // namespace sk

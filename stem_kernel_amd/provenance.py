@@ -14,11 +14,16 @@ import os
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # what the measured kernels' traffic depends on: the kernels, the packing and
-# dispatch (sk_api.cpp, host/pairs_dag.cpp and their headers), the example
-# builder and synthetic inputs
+# dispatch (sk_api.cpp, the host runtime's files under host/ and their
+# headers), the example builder and synthetic inputs
 _SRC_DIRS = ("stem_kernel_amd/csrc/kernels",)
 _SRC_FILES = ("stem_kernel_amd/csrc/sk_api.cpp", "stem_kernel_amd/csrc/host/runtime.h",
               "stem_kernel_amd/csrc/host/runtime_types.h", "stem_kernel_amd/csrc/host/pairs_dag.cpp",
+              "stem_kernel_amd/csrc/host/context.cpp", "stem_kernel_amd/csrc/host/pack.cpp",
+              "stem_kernel_amd/csrc/host/dataset.cpp", "stem_kernel_amd/csrc/host/dataset_io.cpp",
+              "stem_kernel_amd/csrc/host/fold_gpu.cpp", "stem_kernel_amd/csrc/host/pairs_bpla.cpp",
+              "stem_kernel_amd/csrc/host/pairs_la_protein.cpp", "stem_kernel_amd/csrc/host/pairs_simpal.cpp",
+              "stem_kernel_amd/csrc/host/pairs_stem4d.cpp",
               "stem_kernel_amd/csrc/host/example_build.cpp",
               "stem_kernel_amd/csrc/host/synth.cpp", "stem_kernel_amd/csrc/host/sk_internal.h",
               "stem_kernel_amd/csrc/ribosum85_60.inc")

@@ -1,4 +1,4 @@
-"""The batch driver the three GPU folds share (sk_api.cpp fold_batches; host
+"""The batch driver the three GPU folds share (host/fold_gpu.cpp fold_batches; host
 pieces in csrc/host/fold_host.cpp): a call whose items do not fit the memory
 budget together is split into batches, and the packed outputs, ln Z, the
 sampled structures and the sampler's generator key (the sequence's index in

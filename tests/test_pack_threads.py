@@ -1,4 +1,4 @@
-"""The dataset packing (sk_api.cpp pack_dataset) runs its per-example passes
+"""The dataset packing (host/pack.cpp pack_dataset) runs its per-example passes
 on host threads and appends at prefix offsets: the packed arrays must not
 depend on the thread count.  tools/pack_compare.cpp calls the library's
 sk::pack_dataset (host/runtime_types.h) and hashes every packed array (the

@@ -147,7 +147,7 @@ def test_stem4d_params_and_predict(gpu_ctx):
 
 @pytest.mark.gpu
 def test_stem4d_resident_tables_two_datasets(gpu_ctx):
-    """The per-example tables stay resident per dataset (sk_api.cpp
+    """The per-example tables stay resident per dataset (host/pairs_stem4d.cpp
     stem4d_dataset_tables): test x train across two datasets reads each side
     from its own dataset's tables, and a new bp model or loop rebuilds them
     (the same datasets first under NormalBasePair loop 3, then -p, then

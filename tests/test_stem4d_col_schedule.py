@@ -51,7 +51,7 @@ def row_off(m, d2):
 
 
 def bpdiag(seq, bpp):
-    """stem4d_tables: prob(a, a+e) by diagonal, float (sk_api.cpp)."""
+    """stem4d_tables: prob(a, a+e) by diagonal, float (host/pairs_stem4d.cpp)."""
     L = len(seq)
     tri = {}
     k = 0
@@ -371,7 +371,7 @@ def test_library_col_shape_matches_schedule_limits():
 
 
 def _col_cpl(m):
-    # the column kernel's class for |y| = m (sk_api.cpp: |y| < 64, 128, 256, 512)
+    # the column kernel's class for |y| = m (host/pairs_stem4d.cpp: |y| < 64, 128, 256, 512)
     return next(c for c in (1, 2, 4, 8) if m < 64 * c)
 
 

@@ -1,5 +1,5 @@
 // Host packing check (CPU only): packs a synthetic dataset with the
-// sk::pack_dataset of the library it links (sk_api.cpp) and prints the
+// sk::pack_dataset of the library it links (host/pack.cpp) and prints the
 // hashes of the packed arrays and the pack time.  To compare two versions,
 // build each version's own tools/pack_compare.cpp in its tree against that
 // tree's library (make lib) and run both, e.g.
