@@ -555,13 +555,29 @@ const char *sk_svm_last_error(void);
  * GPU one workgroup per problem (csrc/kernels/svm_smo.hip), on the host one
  * thread per problem (csrc/host/svm_train.cpp).
  *
- * WITHOUT SHRINKING.  The active set is always the whole problem and no index
- * is swapped, so the sequence of working pairs is a function of the inputs and
- * both paths give the alphas of the reference's Solve(..., shrinking = 0) bit
- * for bit.  `svm-train` defaults to -h 1 and gradient.cpp hardcodes
- * shrinking = 1 (:224): such a run ends within the same stopping tolerance
- * but not at the same bits (on a 1,040-example Gram with C = 10, eps = 1e-3:
- * obj differs by 2e-8 relative, rho by 2e-4).
+ * SHRINKING is a flag of the call (sk_svm_train_batch_ex; the calls without
+ * _ex run without it).  Both modes are the reference's own runs bit for bit:
+ * alphas, rho, obj and the number of updates of Solve(..., shrinking = 0) and
+ * of Solve(..., shrinking = 1), the latter being what `svm-train` runs by
+ * default (-h 1) and what gradient.cpp hardcodes (:224).  The two runs end
+ * within the same stopping tolerance but not at the same bits (int300 C = 1
+ * of tests/golden: 719 updates against 706, rho differs by 4e-4 relative;
+ * DESIGN.md).
+ *   Without: the active set is always the whole problem and no index is
+ *   swapped, so the sequence of working pairs is a function of the inputs.
+ *   With: every min(l, 1000) updates do_shrinking (solver.cpp:475-552) moves
+ *   the variables at a bound whose gradient rules them out to the tail of a
+ *   permuted problem (swap_index, :47-57) and the selection, the G update and
+ *   rho run over the active prefix (:368, :393, :272, :561).  G_bar (:279-306)
+ *   follows every upper-bound flip over all l positions, i before j;
+ *   reconstruct_gradient (:61-79) rebuilds the inactive G[j] from G_bar[j] +
+ *   p[j] plus alpha_i Q_i[j] over the free active positions i in ascending
+ *   position order, two roundings per term; the unshrink branch runs once,
+ *   when Gmax1 + Gmax2 <= 10 eps, on the reconstructed gradient with the Gmax
+ *   values from before; an optimal selection on a shrunk set reconstructs,
+ *   restores the whole set and selects again (:154-165).  The sums of rho and
+ *   obj, and the last-index rule of the selection, follow the permuted
+ *   positions (:309-327); the alphas go back through active_set.
  *
  * Arithmetic kept from the reference:
  *   Q_i[k] = (float)(y_i y_k K[t_i][t_k]), QD[k] = (float)K[t_k][t_k]
@@ -618,6 +634,35 @@ int sk_svm_train_batch(sk_context *ctx, const double *gram, int32_t n, const dou
 int sk_svm_train_batch_host(const double *gram, int32_t n, const double *labels,
                             const sk_svm_problem *problems, int32_t n_problems, int32_t n_threads,
                             double *alpha_out, double *dec_out, sk_svm_solution *solutions);
+/* What a solve with shrinking did, per problem.  A shrink call "shrank" when
+ * it left fewer active positions than it found; the call that ran the
+ * unshrink branch "regrew" the set when it left more than it found. */
+typedef struct {
+  int32_t shrink_calls;    /* do_shrinking() calls */
+  int32_t shrunk_calls;    /* of those, calls that lowered active_size */
+  int32_t min_active;      /* smallest active_size seen (n_train if none) */
+  int32_t unshrunk;        /* the one-time unshrink branch ran */
+  int32_t regrown;         /* ... and raised active_size */
+  int32_t reconstructions; /* selections that reported optimal with active_size < l */
+  int32_t resumed;         /* of those, followed by a further iteration */
+} sk_svm_shrink_info;
+/* sk_svm_train_batch / _host with the shrinking flag (0 or 1) and, when info
+ * is not NULL, n_problems records of what the shrinking did.  shrinking = 0
+ * is the call without _ex bit for bit, with min_active = n_train and zeros
+ * elsewhere in info.  The same checks, errors and launch counts.  With
+ * shrinking, solutions[p].iterations still counts updates, and max_iter ends
+ * a solve as the reference would end at its optimum: once max_iter updates
+ * have run and a further pair was found, the gradient is reconstructed, the
+ * active set restored, and rho, obj and the alphas are those of that state
+ * (SK_SVM_NOT_CONVERGED). */
+int sk_svm_train_batch_ex(sk_context *ctx, const double *gram, int32_t n, const double *labels,
+                          const sk_svm_problem *problems, int32_t n_problems, int32_t shrinking,
+                          double *alpha_out, double *dec_out, sk_svm_solution *solutions,
+                          sk_svm_shrink_info *info);
+int sk_svm_train_batch_host_ex(const double *gram, int32_t n, const double *labels,
+                               const sk_svm_problem *problems, int32_t n_problems, int32_t n_threads,
+                               int32_t shrinking, double *alpha_out, double *dec_out,
+                               sk_svm_solution *solutions, sk_svm_shrink_info *info);
 /* Size classes of the GPU solver: class c takes n_train <= bounds[c]
  * (ascending; up to 4 written), *n_classes of them, *max_train the last. */
 int sk_svm_train_shape(int32_t *bounds, int32_t *n_classes, int32_t *max_train);

@@ -59,6 +59,11 @@ class AucProblem(C.Structure):  # sk_auc_problem
                 ("delta", C.POINTER(C.c_double))]
 
 
+class SvmShrinkInfo(C.Structure):  # sk_svm_shrink_info
+    _fields_ = [(k, C.c_int32) for k in ("shrink_calls", "shrunk_calls", "min_active", "unshrunk", "regrown",
+                                         "reconstructions", "resumed")]
+
+
 class AucInfo(C.Structure):  # sk_auc_info
     _fields_ = [("n_free", C.c_int32), ("n_bound", C.c_int32), ("cg_iterations", C.c_int32),
                 ("finite", C.c_int32)]
@@ -180,6 +185,11 @@ SIGNATURES = {
                                      C.POINTER(SvmSolution)]),
     "sk_svm_train_batch_host": (C.c_int, [_F64P, C.c_int32, _F64P, C.POINTER(SvmProblem), C.c_int32, C.c_int32,
                                           _F64P, _F64P, C.POINTER(SvmSolution)]),
+    "sk_svm_train_batch_ex": (C.c_int, [_P, _F64P, C.c_int32, _F64P, C.POINTER(SvmProblem), C.c_int32, C.c_int32,
+                                        _F64P, _F64P, C.POINTER(SvmSolution), C.POINTER(SvmShrinkInfo)]),
+    "sk_svm_train_batch_host_ex": (C.c_int, [_F64P, C.c_int32, _F64P, C.POINTER(SvmProblem), C.c_int32, C.c_int32,
+                                             C.c_int32, _F64P, _F64P, C.POINTER(SvmSolution),
+                                             C.POINTER(SvmShrinkInfo)]),
     "sk_svm_train_shape": (C.c_int, [_I32P, _I32P, _I32P]),
     "sk_svm_model_write": (C.c_int, [C.c_char_p, _F64P, C.c_int32, _I32P, C.c_int32, _F64P, C.c_double]),
     "sk_auc_delta": (C.c_int, [_F64P, _F64P, C.c_int32, _F64P, _F64P]),

@@ -24,8 +24,9 @@
 //   ARISING IN ANY WAY OUT OF THE USE OF THIS SOFTWARE, EVEN IF ADVISED OF
 //   THE POSSIBILITY OF SUCH DAMAGE.
 //
-// Two-class C-SVC training on a precomputed Gram: the reference's SMO solver
-// without shrinking, restated from the published algorithm (Fan, Chen and
+// Two-class C-SVC training on a precomputed Gram: the reference's SMO solver,
+// without shrinking (solve_one) and with it (solve_one_shrink, which lists
+// what it adds), restated from the published algorithm (Fan, Chen and
 // Lin, JMLR 6 (2005), working-set selection 3):
 //   Solver::Solve            libsvm/solver.cpp:81-349   (start :113-135, the
 //                            two-variable update :180-265, G update :272-275,
@@ -42,8 +43,8 @@
 // change nothing (solver.cpp:154-165), G_bar is never read, and the Q cache
 // (a store of rows, qmatrix.cpp:37-60) does not touch a value.
 //
-// This file is the CPU path of sk_svm_train_batch, what tests/golden/
-// svm_train.json pins, and what the GPU kernel (kernels/svm_smo.hip) is
+// This file is the CPU path of sk_svm_train_batch[_ex], what tests/golden/
+// svm_train.json and svm_train_shrink.json pin, and what the GPU kernel (kernels/svm_smo.hip) is
 // compared with.  Built with -ffp-contract=off: the G update has four
 // roundings.
 #include "svm_train.h"
@@ -84,6 +85,49 @@ struct Smo {
     for (int k = 0; k < l; ++k) q[k] = (float)(yi * y[k] * r[t[k]]);
   }
 };
+
+// The clipped two-variable update (solver.cpp:180-265) on alpha_i, alpha_j:
+// opposite labels or equal ones; quad_coef in float arithmetic.
+void update_pair(bool opposite, float Qii, float Qjj, float Qij, double Gi, double Gj, double Ci, double Cj,
+                 double& ai, double& aj) {
+  if (opposite) {
+    const float qf = Qii + Qjj + 2 * Qij;
+    double qc = qf;
+    if (qc <= 0) qc = kTau;
+    const double delta = (-Gi - Gj) / qc;
+    const double diff = ai - aj;
+    ai += delta;
+    aj += delta;
+    if (diff > 0) {
+      if (aj < 0) aj = 0, ai = diff;
+    } else {
+      if (ai < 0) ai = 0, aj = -diff;
+    }
+    if (diff > Ci - Cj) {
+      if (ai > Ci) ai = Ci, aj = Ci - diff;
+    } else {
+      if (aj > Cj) aj = Cj, ai = Cj + diff;
+    }
+  } else {
+    const float qf = Qii + Qjj - 2 * Qij;
+    double qc = qf;
+    if (qc <= 0) qc = kTau;
+    const double delta = (Gi - Gj) / qc;
+    const double sum = ai + aj;
+    ai -= delta;
+    aj += delta;
+    if (sum > Ci) {
+      if (ai > Ci) ai = Ci, aj = sum - Ci;
+    } else {
+      if (aj < 0) aj = 0, ai = sum;
+    }
+    if (sum > Cj) {
+      if (aj > Cj) aj = Cj, ai = sum - Cj;
+    } else {
+      if (ai < 0) ai = 0, aj = sum;
+    }
+  }
+}
 
 void solve_one(const double* K, int32_t n, const double* labels, const sk_svm_problem& P, double* alpha,
                double* dec, sk_svm_solution& S) {
@@ -159,43 +203,7 @@ void solve_one(const double* K, int32_t n, const double* labels, const sk_svm_pr
 
     const double Ci = s.bound(i), Cj = s.bound(j);
     const double ai0 = alpha[i], aj0 = alpha[j];
-    if (y[i] != y[j]) {
-      const float qf = Qi[i] + Qj[j] + 2 * Qi[j];
-      double qc = qf;
-      if (qc <= 0) qc = kTau;
-      const double delta = (-G[i] - G[j]) / qc;
-      const double diff = alpha[i] - alpha[j];
-      alpha[i] += delta;
-      alpha[j] += delta;
-      if (diff > 0) {
-        if (alpha[j] < 0) alpha[j] = 0, alpha[i] = diff;
-      } else {
-        if (alpha[i] < 0) alpha[i] = 0, alpha[j] = -diff;
-      }
-      if (diff > Ci - Cj) {
-        if (alpha[i] > Ci) alpha[i] = Ci, alpha[j] = Ci - diff;
-      } else {
-        if (alpha[j] > Cj) alpha[j] = Cj, alpha[i] = Cj + diff;
-      }
-    } else {
-      const float qf = Qi[i] + Qj[j] - 2 * Qi[j];
-      double qc = qf;
-      if (qc <= 0) qc = kTau;
-      const double delta = (G[i] - G[j]) / qc;
-      const double sum = alpha[i] + alpha[j];
-      alpha[i] -= delta;
-      alpha[j] += delta;
-      if (sum > Ci) {
-        if (alpha[i] > Ci) alpha[i] = Ci, alpha[j] = sum - Ci;
-      } else {
-        if (alpha[j] < 0) alpha[j] = 0, alpha[i] = sum;
-      }
-      if (sum > Cj) {
-        if (alpha[j] > Cj) alpha[j] = Cj, alpha[i] = sum - Cj;
-      } else {
-        if (alpha[i] < 0) alpha[i] = 0, alpha[j] = sum;
-      }
-    }
+    update_pair(y[i] != y[j], Qi[i], Qj[j], Qi[j], G[i], G[j], Ci, Cj, alpha[i], alpha[j]);
     const double dai = alpha[i] - ai0, daj = alpha[j] - aj0;
     for (int k = 0; k < l; ++k) G[k] += Qi[k] * dai + Qj[k] * daj;
     s.status(i);
@@ -233,6 +241,277 @@ void solve_one(const double* K, int32_t n, const double* labels, const sk_svm_pr
     double sum = 0.0;
     for (int a = 0; a < l; ++a)
       if (alpha[a] != 0.0) sum += alpha[a] * y[a] * r[s.t[a]];
+    dec[q] = sum - S.rho;
+  }
+}
+
+// ---- the same solver with libsvm's shrinking (Solve(..., shrinking = 1)).
+// The reference permutes the problem while it runs (swap_index,
+// solver.cpp:47-57); here every array is indexed by *position*, t[k] is the
+// Gram index and aset[k] the training-list index of the example at position
+// k.  What decides the bits beyond the solver above:
+//   - selection, the G update and rho run over the positions < active; ties
+//     go to the last position (solver.cpp:368-443, :272-275, :561);
+//   - Gb (G_bar) takes +- C_i Q_i[k] over all l positions when i enters or
+//     leaves its upper bound, i before j, two roundings per entry (:279-306);
+//   - reconstruct (:61-79): G[j] = Gb[j] + p[j], then + alpha_i Q_i[j] for the
+//     free active positions i in ascending order, two roundings per term;
+//   - shrink (:475-552): the two-pointer loop from both ends, and once, when
+//     Gmax1 + Gmax2 <= 10 eps, reconstruct and the mirror loop from the tail
+//     with the Gmax values from before;
+//   - counter (:139-165) and the epilogue (:309-327) over the positions.
+// Q_i[k] = (float)(y y K[t_i][t_k]) of the current occupants: the reference's
+// row cache (qmatrix.cpp:37-60, Cache::swap_index) stores such values and
+// changes none.
+struct ShrinkSmo {
+  const double* K;
+  size_t n;
+  int l, active;
+  double Cp, Cn, eps;
+  int64_t max_iter, iter = 0;
+  std::vector<int32_t> t, aset;
+  std::vector<signed char> y;
+  std::vector<float> QD, Qi, Qj;
+  std::vector<double> G, Gb, alpha;
+  std::vector<char> st;
+  bool unshrunk = false, stopped = false, pending = false;
+  int32_t status = SK_SVM_CONVERGED;
+  sk_svm_shrink_info info;
+
+  double bound(int k) const { return y[k] > 0 ? Cp : Cn; }
+  void set_status(int k) { st[k] = alpha[k] >= bound(k) ? kUpper : alpha[k] <= 0 ? kLower : kFree; }
+  void row(int i, std::vector<float>& q, int len) const {
+    const double* r = K + (size_t)t[i] * n;
+    const int yi = y[i];
+    for (int k = 0; k < len; ++k) q[k] = (float)(yi * y[k] * r[t[k]]);
+  }
+  void swap_positions(int a, int b) {
+    std::swap(t[a], t[b]);
+    std::swap(QD[a], QD[b]);
+    std::swap(y[a], y[b]);
+    std::swap(G[a], G[b]);
+    std::swap(st[a], st[b]);
+    std::swap(alpha[a], alpha[b]);
+    std::swap(aset[a], aset[b]);
+    std::swap(Gb[a], Gb[b]);
+  }
+
+  // the working pair over the active positions; false: optimal.  Leaves row i in Qi.
+  bool pair(int& i, int& j) {
+    double gmax = -kInf, gmax2 = -kInf, od_min = kInf;
+    i = -1, j = -1;
+    for (int k = 0; k < active; ++k) {
+      if (y[k] > 0) {
+        if (st[k] != kUpper && -G[k] >= gmax) gmax = -G[k], i = k;
+      } else {
+        if (st[k] != kLower && G[k] >= gmax) gmax = G[k], i = k;
+      }
+    }
+    if (i >= 0) row(i, Qi, active);
+    for (int k = 0; k < active; ++k) {
+      double gd;
+      float qf;
+      if (y[k] > 0) {
+        if (st[k] == kLower) continue;
+        gd = gmax + G[k];
+        if (G[k] >= gmax2) gmax2 = G[k];
+        if (!(gd > 0)) continue;
+        qf = Qi[i] + QD[k] - 2 * y[i] * Qi[k];  // float arithmetic
+      } else {
+        if (st[k] == kUpper) continue;
+        gd = gmax - G[k];
+        if (-G[k] >= gmax2) gmax2 = -G[k];
+        if (!(gd > 0)) continue;
+        qf = Qi[i] + QD[k] + 2 * y[i] * Qi[k];
+      }
+      const double qc = qf;
+      const double od = qc > 0 ? -(gd * gd) / qc : -(gd * gd) / kTau;
+      if (od <= od_min) od_min = od, j = k;
+    }
+    return !(gmax + gmax2 < eps);
+  }
+
+  // pair() with the iteration cap and the counters: once max_iter updates
+  // have run and a further pair was found (or none can be), this and every
+  // later selection report optimal, so the loop below reconstructs the
+  // gradient, restores the active set and ends
+  bool select(int& i, int& j) {
+    if (stopped) return false;
+    const bool after_reconstruction = pending;
+    pending = false;
+    if (!pair(i, j)) {
+      if (active < l) ++info.reconstructions, pending = true;
+      return false;
+    }
+    if (i < 0 || j < 0) {
+      status = SK_SVM_NO_PAIR, stopped = true;
+      return false;
+    }
+    if (iter == max_iter) {
+      status = SK_SVM_NOT_CONVERGED, stopped = true;
+      return false;
+    }
+    if (after_reconstruction) ++info.resumed;
+    return true;
+  }
+
+  void reconstruct() {
+    if (active == l) return;
+    for (int k = active; k < l; ++k) G[k] = Gb[k] + -1.0;
+    for (int i = 0; i < active; ++i)
+      if (st[i] == kFree) {
+        row(i, Qi, l);
+        const double a = alpha[i];
+        for (int k = active; k < l; ++k) G[k] += a * Qi[k];
+      }
+  }
+
+  bool shrinkable(int k, double g1, double g2) const {
+    if (st[k] == kUpper) return y[k] > 0 ? -G[k] > g1 : -G[k] > g2;
+    if (st[k] == kLower) return y[k] > 0 ? G[k] > g2 : G[k] > g1;
+    return false;
+  }
+
+  void shrink() {
+    ++info.shrink_calls;
+    const int before = active;
+    double g1 = -kInf, g2 = -kInf;  // max of -y G over I_up, of y G over I_low
+    for (int k = 0; k < active; ++k) {
+      if (y[k] > 0) {
+        if (st[k] != kUpper && -G[k] >= g1) g1 = -G[k];
+        if (st[k] != kLower && G[k] >= g2) g2 = G[k];
+      } else {
+        if (st[k] != kUpper && -G[k] >= g2) g2 = -G[k];
+        if (st[k] != kLower && G[k] >= g1) g1 = G[k];
+      }
+    }
+    for (int k = 0; k < active; ++k)
+      if (shrinkable(k, g1, g2))
+        for (--active; active > k; --active)
+          if (!shrinkable(active, g1, g2)) {
+            swap_positions(k, active);
+            break;
+          }
+    if (!unshrunk && !(g1 + g2 > eps * 10)) {
+      unshrunk = true;
+      info.unshrunk = 1;
+      reconstruct();
+      for (int k = l - 1; k >= active; --k)
+        if (!shrinkable(k, g1, g2)) {
+          for (; active < k; ++active)
+            if (shrinkable(active, g1, g2)) {
+              swap_positions(k, active);
+              break;
+            }
+          ++active;
+        }
+      if (active > before) info.regrown = 1;
+    }
+    if (active < before) ++info.shrunk_calls;
+    info.min_active = std::min(info.min_active, active);
+  }
+};
+
+void solve_one_shrink(const double* K, int32_t n, const double* labels, const sk_svm_problem& P, double* alpha_out,
+                      double* dec, sk_svm_solution& S, sk_svm_shrink_info& info) {
+  ShrinkSmo s;
+  s.K = K;
+  s.n = (size_t)n;
+  const int l = s.l = s.active = P.n_train;
+  s.Cp = P.Cp, s.Cn = P.Cn, s.eps = P.eps, s.max_iter = P.max_iter;
+  s.info = sk_svm_shrink_info{0, 0, l, 0, 0, 0, 0};
+  s.t.assign(P.train, P.train + l);
+  s.aset.resize(l);
+  s.y.resize(l);
+  s.QD.resize(l);
+  s.Qi.resize(l);
+  s.Qj.resize(l);
+  s.G.assign(l, -1.0);
+  s.Gb.assign(l, 0.0);
+  s.alpha.assign(l, 0.0);
+  s.st.assign(l, kLower);
+  for (int k = 0; k < l; ++k) {
+    s.aset[k] = k;
+    s.y[k] = labels[s.t[k]] > 0 ? +1 : -1;
+    s.QD[k] = (float)K[(size_t)s.t[k] * s.n + s.t[k]];
+  }
+  std::vector<double>&G = s.G, &Gb = s.Gb, &alpha = s.alpha;
+  const std::vector<float>&Qi = s.Qi, &Qj = s.Qj;
+
+  const int period = std::min(l, 1000);
+  int counter = period + 1;
+  for (;;) {
+    if (--counter == 0) {
+      counter = period;
+      s.shrink();
+    }
+    int i, j;
+    if (!s.select(i, j)) {
+      s.reconstruct();
+      s.active = l;
+      if (!s.select(i, j)) break;
+      counter = 1;  // shrink at the next iteration
+    }
+    ++s.iter;
+    const int active = s.active;
+    s.row(j, s.Qj, active);  // row i is in Qi since the selection
+    const double Ci = s.bound(i), Cj = s.bound(j);
+    const double ai0 = alpha[i], aj0 = alpha[j];
+    update_pair(s.y[i] != s.y[j], Qi[i], Qj[j], Qi[j], G[i], G[j], Ci, Cj, alpha[i], alpha[j]);
+    const double dai = alpha[i] - ai0, daj = alpha[j] - aj0;
+    for (int k = 0; k < active; ++k) G[k] += Qi[k] * dai + Qj[k] * daj;
+    const bool ui = s.st[i] == kUpper, uj = s.st[j] == kUpper;
+    s.set_status(i);
+    s.set_status(j);
+    if (ui != (s.st[i] == kUpper)) {
+      s.row(i, s.Qi, l);
+      if (ui)
+        for (int k = 0; k < l; ++k) Gb[k] -= Ci * Qi[k];
+      else
+        for (int k = 0; k < l; ++k) Gb[k] += Ci * Qi[k];
+    }
+    if (uj != (s.st[j] == kUpper)) {
+      s.row(j, s.Qj, l);
+      if (uj)
+        for (int k = 0; k < l; ++k) Gb[k] -= Cj * Qj[k];
+      else
+        for (int k = 0; k < l; ++k) Gb[k] += Cj * Qj[k];
+    }
+  }
+
+  // rho, obj: in position order; the alphas go back to training order
+  int n_free = 0, n_bound = 0;
+  double ub = kInf, lb = -kInf, sum_free = 0;
+  for (int k = 0; k < l; ++k) {
+    const double yg = s.y[k] * G[k];
+    if (s.st[k] == kUpper) {
+      ++n_bound;
+      if (s.y[k] < 0) ub = std::min(ub, yg);
+      else lb = std::max(lb, yg);
+    } else if (s.st[k] == kLower) {
+      if (s.y[k] > 0) ub = std::min(ub, yg);
+      else lb = std::max(lb, yg);
+    } else {
+      ++n_free;
+      sum_free += yg;
+    }
+  }
+  S.rho = n_free > 0 ? sum_free / n_free : (ub + lb) / 2;
+  double v = 0;
+  for (int k = 0; k < l; ++k) v += alpha[k] * (G[k] + -1.0);
+  S.obj = v / 2;
+  S.iterations = s.iter;
+  S.status = s.status;
+  S.n_free = n_free;
+  S.n_bound = n_bound;
+  info = s.info;
+  for (int k = 0; k < l; ++k) alpha_out[s.aset[k]] = alpha[k];
+
+  for (int q = 0; q < P.n_test; ++q) {
+    const double* r = K + (size_t)P.test[q] * s.n;
+    double sum = 0.0;
+    for (int a = 0; a < l; ++a)
+      if (alpha_out[a] != 0.0) sum += alpha_out[a] * (labels[P.train[a]] > 0 ? 1 : -1) * r[P.train[a]];
     dec[q] = sum - S.rho;
   }
 }
@@ -294,9 +573,9 @@ int svm_check_batch(const double* gram, int32_t n, const double* labels, const s
 
 extern "C" {
 
-int sk_svm_train_batch_host(const double* gram, int32_t n, const double* labels, const sk_svm_problem* problems,
-                            int32_t n_problems, int32_t n_threads, double* alpha_out, double* dec_out,
-                            sk_svm_solution* solutions) {
+int sk_svm_train_batch_host_ex(const double* gram, int32_t n, const double* labels, const sk_svm_problem* problems,
+                               int32_t n_problems, int32_t n_threads, int32_t shrinking, double* alpha_out,
+                               double* dec_out, sk_svm_solution* solutions, sk_svm_shrink_info* info) {
   try {
     std::string err;
     int64_t st = 0, ss = 0;
@@ -316,8 +595,13 @@ int sk_svm_train_batch_host(const double* gram, int32_t n, const double* labels,
     auto work = [&] {
       for (int p; (p = cursor.fetch_add(1)) < n_problems;) {
         try {
-          solve_one(gram, n, labels, problems[p], alpha_out + aoff[p], dec_out ? dec_out + doff[p] : nullptr,
-                    solutions[p]);
+          double* dec = dec_out ? dec_out + doff[p] : nullptr;
+          sk_svm_shrink_info si = {0, 0, problems[p].n_train, 0, 0, 0, 0};
+          if (shrinking)
+            solve_one_shrink(gram, n, labels, problems[p], alpha_out + aoff[p], dec, solutions[p], si);
+          else
+            solve_one(gram, n, labels, problems[p], alpha_out + aoff[p], dec, solutions[p]);
+          if (info) info[p] = si;
         } catch (const std::bad_alloc&) {
           oom = true;
         }
@@ -337,6 +621,13 @@ int sk_svm_train_batch_host(const double* gram, int32_t n, const double* labels,
   } catch (const std::bad_alloc&) {
     return SK_ERR_ALLOC;
   }
+}
+
+int sk_svm_train_batch_host(const double* gram, int32_t n, const double* labels, const sk_svm_problem* problems,
+                            int32_t n_problems, int32_t n_threads, double* alpha_out, double* dec_out,
+                            sk_svm_solution* solutions) {
+  return sk_svm_train_batch_host_ex(gram, n, labels, problems, n_problems, n_threads, 0, alpha_out, dec_out,
+                                    solutions, nullptr);
 }
 
 int sk_svm_train_shape(int32_t* bounds, int32_t* n_classes, int32_t* max_train) {

@@ -1,9 +1,11 @@
-// Batched C-SVC training on CDNA4 (gfx950): libsvm's SMO solver without
-// shrinking, one workgroup per (training subset, C) problem over one Gram
-// resident in device memory.
+// Batched C-SVC training on CDNA4 (gfx950): libsvm's SMO solver, without
+// shrinking or with it (two instantiations of one kernel), one workgroup per
+// (training subset, C) problem over one Gram resident in device memory.
 //
 // Reference: Solver::Solve  libsvm/solver.cpp:81-349, select_working_set
-//   :352-451, calculate_rho :554-592, SVC_Q libsvm/qmatrix.cpp:339-362; the
+//   :352-451, calculate_rho :554-592, SVC_Q libsvm/qmatrix.cpp:339-362; with
+//   shrinking also swap_index :47-57, reconstruct_gradient :61-79,
+//   do_shrinking :475-552; the
 //   arithmetic contract is the one csrc/host/svm_train.cpp restates (float Q
 //   entries and quad_coef, double everything else, no fused multiply-add),
 //   and the alphas are that file's bit for bit: every rounded operation below
@@ -39,8 +41,33 @@
 // one wave per test example, lanes over the training examples, a butterfly
 // sum -- the one place where the order of a sum differs from the host's.
 //
+// Shrinking (SHRINK = true; csrc/host/svm_train.cpp: ShrinkSmo is the same
+// restated on the host).  "Element k" above becomes "position k" of the
+// reference's permuted problem: a thread's registers hold whatever example
+// occupies its positions, with that example's training index (aset) and
+// G_bar next to G.  Steps 1, 2 and 4 run over the positions < active.  When
+// alpha_i or alpha_j enters or leaves its upper bound (known to every thread:
+// the status is a function of alpha), every thread adds -+ C Q[k] to its
+// G_bar over all l positions, reading the row's entries of its inactive
+// positions too.  Every min(l, 1000) iterations a shrink event: Gmax1 and
+// Gmax2 by exact max reductions; every thread writes be_shrunken of its
+// positions as a byte to LDS; thread 0 runs the reference's two-pointer loop
+// on the bytes, swapping them as the reference swaps state and recording the
+// swaps in a permutation; then every thread gathers its state through that
+// permutation, one array at a time through LDS (nothing to gather when no
+// swap was made, the common case).  The serial part is O(l) LDS operations
+// per event and stays serial.  reconstruct_gradient: the free active alphas
+// go to LDS by position (-1 elsewhere), every thread walks the positions in
+// ascending order -- a uniform loop -- and adds alpha_i Q_i[j] to the G of
+// its inactive positions, so every G[j] receives its terms in the
+// reference's order with two roundings each.  The unshrink branch is
+// reconstruct, fresh bytes, the mirror loop from the tail and the gather
+// again.  The epilogue's sequential sums run over positions, which is the
+// reference's order; alphas are written to their training indices.
+//
 // LDS per workgroup: 12 bytes per element slot (48 KiB in the largest class)
-// and the waves' records.  No atomics, no inline assembly.
+// and the waves' records; the shrink event reuses the slots.  No atomics, no
+// inline assembly.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -70,6 +97,7 @@ struct SvmLaunch {
   double* alpha;
   double* dec;
   sk_svm_solution* sol;
+  sk_svm_shrink_info* info;  // written by the shrinking solver only
 };
 
 struct RecI {  // a wave's candidate for i
@@ -88,7 +116,9 @@ enum : int { kStLower = 0, kStUpper = 1, kStFree = 2, kStAbsent = 3 };
 
 __device__ __forceinline__ double shfl_xor_f64(double v, int m) { return __shfl_xor(v, m, 64); }
 
-template <int T>
+// SHRINK: libsvm's shrinking (Solve(..., shrinking = 1)); its additions are
+// described above ("Shrinking") and compiled into that instantiation only.
+template <int T, bool SHRINK>
 __global__ void __launch_bounds__(T) sk_svm_smo_kernel(SvmLaunch L) {
   constexpr int E = kSvmElems, W = T / 64, CAP = T * E;
   __shared__ double s_val[CAP];
@@ -110,10 +140,14 @@ __global__ void __launch_bounds__(T) sk_svm_smo_kernel(SvmLaunch L) {
   int tk[E], yk[E], st[E];
   float qd[E], qi[E], qj[E];
   double G[E], al[E];
+  // SHRINK: position k = e * T + tid holds training example aset[e]; Gb is G_bar
+  int aset[E];
+  double Gb[E];
 #pragma unroll
   for (int e = 0; e < E; ++e) {
     const int k = e * T + tid;
     tk[e] = 0, yk[e] = 1, st[e] = kStAbsent, qd[e] = 0.f, qi[e] = 0.f, qj[e] = 0.f, G[e] = 0.0, al[e] = 0.0;
+    aset[e] = k, Gb[e] = 0.0;
     if (k < l) {
       const int t = tr[k];
       tk[e] = t;
@@ -128,13 +162,197 @@ __global__ void __launch_bounds__(T) sk_svm_smo_kernel(SvmLaunch L) {
 
   int64_t iter = 0;
   int status = SK_SVM_CONVERGED;
+  // SHRINK: the positions < active are selected from and updated
+  int active = l;
+  auto live = [&](int e) {
+    if constexpr (SHRINK) return e * T + tid < active;
+    else return st[e] != kStAbsent;
+  };
+  sk_svm_shrink_info info = {0, 0, l, 0, 0, 0, 0};
+
+  // s_val[k] = X[position k]; X[e] = s_val[sp[e]]: the state moves to its new positions
+  auto gather = [&](double(&X)[E], const int(&sp)[E]) {
+#pragma unroll
+    for (int e = 0; e < E; ++e)
+      if (st[e] != kStAbsent) s_val[e * T + tid] = X[e];
+    __syncthreads();
+#pragma unroll
+    for (int e = 0; e < E; ++e)
+      if (st[e] != kStAbsent) X[e] = s_val[sp[e]];
+    __syncthreads();
+  };
+  // be_shrunken of every position as a byte in s_val's first CAP bytes, and
+  // the identity permutation as 16-bit entries in the 2 CAP bytes after them
+  static_assert(CAP <= 65536 && CAP % 2 == 0, "positions are 16-bit entries of s_val");
+  unsigned char* const s_flag = reinterpret_cast<unsigned char*>(s_val);
+  unsigned short* const s_src = reinterpret_cast<unsigned short*>(s_val) + CAP / 2;
+  auto write_flags = [&](double g1, double g2) {
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+      if (st[e] == kStAbsent) continue;
+      bool f = false;
+      if (st[e] == kStUpper) f = yk[e] > 0 ? -G[e] > g1 : -G[e] > g2;
+      else if (st[e] == kStLower) f = yk[e] > 0 ? G[e] > g2 : G[e] > g1;
+      s_flag[e * T + tid] = f ? 1 : 0;
+      s_src[e * T + tid] = (unsigned short)(e * T + tid);
+    }
+    __syncthreads();
+  };
+  // after thread 0's serial loop (new active size in s_nf[0], "a swap was
+  // made" in s_nb[0], the permutation in s_src): every array of the state,
+  // one at a time through s_val; status, QD and aset as one 64-bit word
+  auto apply_permutation = [&]() {
+    __syncthreads();
+    active = s_nf[0];
+    if (!s_nb[0]) return;  // uniform
+    int sp[E];
+#pragma unroll
+    for (int e = 0; e < E; ++e) sp[e] = st[e] != kStAbsent ? (int)s_src[e * T + tid] : 0;
+    __syncthreads();
+    gather(G, sp);
+    gather(Gb, sp);
+    gather(al, sp);
+    double w[E];
+#pragma unroll
+    for (int e = 0; e < E; ++e)
+      w[e] = __longlong_as_double(((long long)((aset[e] << 2) | st[e]) << 32) | (long long)__float_as_uint(qd[e]));
+    gather(w, sp);
+    int ty[E];
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+      if (st[e] == kStAbsent) continue;
+      const long long b = __double_as_longlong(w[e]);
+      qd[e] = __uint_as_float((unsigned)(b & 0xffffffffll));
+      st[e] = (int)(b >> 32) & 3;
+      aset[e] = (int)(b >> 34);
+      ty[e] = s_ty[sp[e]];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int e = 0; e < E; ++e)
+      if (st[e] != kStAbsent) s_ty[e * T + tid] = ty[e], tk[e] = ty[e] >> 1, yk[e] = (ty[e] & 1) ? 1 : -1;
+    __syncthreads();
+  };
+  // reconstruct_gradient: G of the positions in [active, l) from G_bar + p
+  // and the free active positions i in ascending order (their alphas by
+  // position in s_val, -1 for the others: the loop over i is uniform), lanes
+  // on consecutive positions of row t_i, two roundings per term
+  auto reconstruct = [&]() {
+    if (active == l) return;  // uniform
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+      if (st[e] == kStAbsent) continue;
+      const int k = e * T + tid;
+      s_val[k] = (k < active && st[e] == kStFree) ? al[e] : -1.0;
+      if (k >= active) G[e] = __dadd_rn(Gb[e], -1.0);
+    }
+    __syncthreads();
+    for (int i = 0; i < active; ++i) {
+      const double a = s_val[i];
+      if (a < 0) continue;
+      const int ty = s_ty[i];
+      const int y_i = (ty & 1) ? 1 : -1;
+      const double* __restrict__ ri = K + (size_t)(ty >> 1) * n;
+#pragma unroll
+      for (int e = 0; e < E; ++e)
+        if (st[e] != kStAbsent && e * T + tid >= active) {
+          const float q = (float)((double)(y_i * yk[e]) * ri[tk[e]]);
+          G[e] = __dadd_rn(G[e], __dmul_rn(a, (double)q));
+        }
+    }
+    __syncthreads();
+  };
+  // do_shrinking
+  bool unshrunk = false;
+  auto shrink_event = [&]() {
+    ++info.shrink_calls;
+    const int before = active;
+    double g1 = -inf, g2 = -inf;  // max of -y G over I_up, of y G over I_low
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+      if (!live(e)) continue;
+      if (yk[e] > 0) {
+        if (st[e] != kStUpper && -G[e] >= g1) g1 = -G[e];
+        if (st[e] != kStLower && G[e] >= g2) g2 = G[e];
+      } else {
+        if (st[e] != kStUpper && -G[e] >= g2) g2 = -G[e];
+        if (st[e] != kStLower && G[e] >= g1) g1 = G[e];
+      }
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+      const double o1 = shfl_xor_f64(g1, m), o2 = shfl_xor_f64(g2, m);
+      g1 = o1 > g1 ? o1 : g1;
+      g2 = o2 > g2 ? o2 : g2;
+    }
+    if (lane == 0) s_ub[wave] = g1, s_lb[wave] = g2;
+    __syncthreads();
+    g1 = -inf, g2 = -inf;
+#pragma unroll
+    for (int w = 0; w < W; ++w) {
+      g1 = s_ub[w] > g1 ? s_ub[w] : g1;
+      g2 = s_lb[w] > g2 ? s_lb[w] : g2;
+    }
+    write_flags(g1, g2);
+    if (tid == 0) {  // the two-pointer loop from both ends
+      int a = active, moved = 0;
+      for (int k = 0; k < a; ++k)
+        if (s_flag[k])
+          for (--a; a > k; --a)
+            if (!s_flag[a]) {
+              s_flag[k] = 0, s_flag[a] = 1;
+              const unsigned short x = s_src[k];
+              s_src[k] = s_src[a], s_src[a] = x;
+              moved = 1;
+              break;
+            }
+      s_nf[0] = a, s_nb[0] = moved;
+    }
+    apply_permutation();
+    if (!unshrunk && !(__dadd_rn(g1, g2) > __dmul_rn(P.eps, 10.0))) {
+      unshrunk = true;
+      info.unshrunk = 1;
+      reconstruct();
+      write_flags(g1, g2);
+      if (tid == 0) {  // the mirror loop from the tail
+        int a = active, moved = 0;
+        for (int k = l - 1; k >= a; --k)
+          if (!s_flag[k]) {
+            for (; a < k; ++a)
+              if (s_flag[a]) {
+                s_flag[k] = 1, s_flag[a] = 0;
+                const unsigned short x = s_src[k];
+                s_src[k] = s_src[a], s_src[a] = x;
+                moved = 1;
+                break;
+              }
+            ++a;
+          }
+        s_nf[0] = a, s_nb[0] = moved;
+      }
+      apply_permutation();
+      if (active > before) info.regrown = 1;
+    }
+    if (active < before) ++info.shrunk_calls;
+    info.min_active = active < info.min_active ? active : info.min_active;
+  };
+  const int period = l < 1000 ? l : 1000;
+  int counter = period + 1;
+  bool again = false, stopped = false, pending = false;
+
   for (;;) {
+    if constexpr (SHRINK) {
+      if (!again && --counter == 0) {
+        counter = period;
+        shrink_event();
+      }
+    }
     // ---- 1. i: the last maximiser of -y G over I_up
     double v = -inf;
     int idx = -1;
 #pragma unroll
     for (int e = 0; e < E; ++e) {
-      if (st[e] == kStAbsent) continue;
+      if (!live(e)) continue;
       const int k = e * T + tid;
       if (yk[e] > 0) {
         if (st[e] != kStUpper && -G[e] >= v) v = -G[e], idx = k;
@@ -174,7 +392,7 @@ __global__ void __launch_bounds__(T) sk_svm_smo_kernel(SvmLaunch L) {
       ri = K + (size_t)(ty >> 1) * n;
 #pragma unroll
       for (int e = 0; e < E; ++e)
-        if (st[e] != kStAbsent) qi[e] = (float)((double)(y_i * yk[e]) * ri[tk[e]]);
+        if (live(e)) qi[e] = (float)((double)(y_i * yk[e]) * ri[tk[e]]);
     }
 
     // ---- 2. j: the last minimiser of the objective's decrease over I_low
@@ -182,7 +400,7 @@ __global__ void __launch_bounds__(T) sk_svm_smo_kernel(SvmLaunch L) {
     int jdx = -1;
 #pragma unroll
     for (int e = 0; e < E; ++e) {
-      if (st[e] == kStAbsent) continue;
+      if (!live(e)) continue;
       double gd;
       float qf;
       if (yk[e] > 0) {
@@ -234,14 +452,44 @@ __global__ void __launch_bounds__(T) sk_svm_smo_kernel(SvmLaunch L) {
     }
 
     // ---- 3. stop, or update alpha_i and alpha_j (every thread, same values)
-    if (__dadd_rn(gmax, gmax2) < P.eps) break;
-    if (i < 0 || j < 0) {
-      status = SK_SVM_NO_PAIR;
-      break;
-    }
-    if (iter == P.max_iter) {
-      status = SK_SVM_NOT_CONVERGED;
-      break;
+    if constexpr (!SHRINK) {
+      if (__dadd_rn(gmax, gmax2) < P.eps) break;
+      if (i < 0 || j < 0) {
+        status = SK_SVM_NO_PAIR;
+        break;
+      }
+      if (iter == P.max_iter) {
+        status = SK_SVM_NOT_CONVERGED;
+        break;
+      }
+    } else {
+      // An optimal selection on a shrunk set is not the end: reconstruct the
+      // gradient, restore the whole set and select again (`again`); a pair
+      // found then resumes the loop, with a shrink at the next iteration.
+      // max_iter (and a missing pair) end the solve the same way: as if the
+      // selection had reported optimal, twice.
+      bool found = false;
+      const bool after_reconstruction = pending;
+      pending = false;
+      if (__dadd_rn(gmax, gmax2) < P.eps) {
+        if (active < l) ++info.reconstructions, pending = true;
+      } else if (i < 0 || j < 0) {
+        status = SK_SVM_NO_PAIR, stopped = true;
+      } else if (iter == P.max_iter) {
+        status = SK_SVM_NOT_CONVERGED, stopped = true;
+      } else {
+        if (after_reconstruction) ++info.resumed;
+        found = true;
+      }
+      if (!found) {
+        if (again) break;
+        reconstruct();
+        active = l;
+        if (stopped) break;
+        again = true;
+        continue;
+      }
+      if (again) counter = 1, again = false;
     }
     ++iter;
     const int tyj = s_ty[j];
@@ -249,7 +497,7 @@ __global__ void __launch_bounds__(T) sk_svm_smo_kernel(SvmLaunch L) {
     const double* __restrict__ rj = K + (size_t)(tyj >> 1) * n;
 #pragma unroll
     for (int e = 0; e < E; ++e)
-      if (st[e] != kStAbsent) qj[e] = (float)((double)(y_j * yk[e]) * rj[tk[e]]);
+      if (live(e)) qj[e] = (float)((double)(y_j * yk[e]) * rj[tk[e]]);
     const float q_ij = (float)((double)(y_i * y_j) * ri[tyj >> 1]);
     const double G_i = y_i > 0 ? -gmax : gmax;
     const double Ci = y_i > 0 ? P.Cp : P.Cn, Cj = y_j > 0 ? P.Cp : P.Cn;
@@ -296,8 +544,30 @@ __global__ void __launch_bounds__(T) sk_svm_smo_kernel(SvmLaunch L) {
     // ---- 4. G, and the owners' alphas
 #pragma unroll
     for (int e = 0; e < E; ++e)
-      if (st[e] != kStAbsent)
+      if (live(e))
         G[e] = __dadd_rn(G[e], __dadd_rn(__dmul_rn((double)qi[e], dai), __dmul_rn((double)qj[e], daj)));
+    if constexpr (SHRINK) {
+      // G_bar: -+ C Q[k] over all l positions when i, then j, leaves or
+      // enters its upper bound (the status is a function of alpha: uniform)
+      if ((ai0 >= Ci) != (ai >= Ci)) {
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+          if (st[e] == kStAbsent) continue;
+          const float q = live(e) ? qi[e] : (float)((double)(y_i * yk[e]) * ri[tk[e]]);
+          const double cq = __dmul_rn(Ci, (double)q);
+          Gb[e] = ai0 >= Ci ? __dsub_rn(Gb[e], cq) : __dadd_rn(Gb[e], cq);
+        }
+      }
+      if ((aj0 >= Cj) != (aj >= Cj)) {
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+          if (st[e] == kStAbsent) continue;
+          const float q = live(e) ? qj[e] : (float)((double)(y_j * yk[e]) * rj[tk[e]]);
+          const double cq = __dmul_rn(Cj, (double)q);
+          Gb[e] = aj0 >= Cj ? __dsub_rn(Gb[e], cq) : __dadd_rn(Gb[e], cq);
+        }
+      }
+    }
     if ((i & (T - 1)) == tid) {
       const int slot = i / T;
 #pragma unroll
@@ -375,6 +645,7 @@ __global__ void __launch_bounds__(T) sk_svm_smo_kernel(SvmLaunch L) {
     S.n_free = nf;
     S.n_bound = nb;
     L.sol[L.which[blockIdx.x]] = S;
+    if constexpr (SHRINK) L.info[L.which[blockIdx.x]] = info;
   }
   __syncthreads();
   // ---- alphas out; decision values of the test list
@@ -382,7 +653,7 @@ __global__ void __launch_bounds__(T) sk_svm_smo_kernel(SvmLaunch L) {
   for (int e = 0; e < E; ++e)
     if (st[e] != kStAbsent) {
       const int k = e * T + tid;
-      L.alpha[P.train_off + k] = al[e];
+      L.alpha[P.train_off + (SHRINK ? aset[e] : k)] = al[e];
       s_val[k] = yk[e] > 0 ? al[e] : -al[e];
     }
   __syncthreads();
@@ -400,8 +671,9 @@ __global__ void __launch_bounds__(T) sk_svm_smo_kernel(SvmLaunch L) {
 }
 
 template <int T>
-hipError_t launch_class(const SvmLaunch& L, int grid, hipStream_t st) {
-  hipLaunchKernelGGL(sk_svm_smo_kernel<T>, dim3(grid), dim3(T), 0, st, L);
+hipError_t launch_class(const SvmLaunch& L, bool shrinking, int grid, hipStream_t st) {
+  if (shrinking) hipLaunchKernelGGL((sk_svm_smo_kernel<T, true>), dim3(grid), dim3(T), 0, st, L);
+  else hipLaunchKernelGGL((sk_svm_smo_kernel<T, false>), dim3(grid), dim3(T), 0, st, L);
   return hipGetLastError();
 }
 
@@ -422,9 +694,10 @@ struct DevBuf {
       return sk::ctx_fail(ctx, SK_ERR_HIP, std::string("sk_svm_train_batch: " #expr ": ") + hipGetErrorString(_e)); \
   } while (0)
 
-extern "C" int sk_svm_train_batch(sk_context* ctx, const double* gram, int32_t n, const double* labels,
-                                  const sk_svm_problem* problems, int32_t n_problems, double* alpha_out,
-                                  double* dec_out, sk_svm_solution* solutions) {
+extern "C" int sk_svm_train_batch_ex(sk_context* ctx, const double* gram, int32_t n, const double* labels,
+                                     const sk_svm_problem* problems, int32_t n_problems, int32_t shrinking,
+                                     double* alpha_out, double* dec_out, sk_svm_solution* solutions,
+                                     sk_svm_shrink_info* info) {
   if (!ctx) return SK_ERR_INVALID;
   try {
     sk::lev_reset(ctx);
@@ -483,7 +756,8 @@ extern "C" int sk_svm_train_batch(sk_context* ctx, const double* gram, int32_t n
     const size_t o_gram = take((size_t)n * n * 8), o_y = take((size_t)n), o_tr = take((size_t)sum_train * 4),
                  o_ts = take((size_t)sum_test * 4), o_pr = take((size_t)n_problems * sizeof(sk::SvmProb)),
                  o_wh = take((size_t)n_problems * 4), o_al = take((size_t)sum_train * 8),
-                 o_de = take((size_t)sum_test * 8), o_so = take((size_t)n_problems * sizeof(sk_svm_solution));
+                 o_de = take((size_t)sum_test * 8), o_so = take((size_t)n_problems * sizeof(sk_svm_solution)),
+                 o_in = take((size_t)n_problems * sizeof(sk_svm_shrink_info));
     sk::DevBuf buf;
     if (hipMalloc(&buf.p, off) != hipSuccess) {
       (void)hipGetLastError();
@@ -509,15 +783,16 @@ extern "C" int sk_svm_train_batch(sk_context* ctx, const double* gram, int32_t n
     L.alpha = reinterpret_cast<double*>(base + o_al);
     L.dec = reinterpret_cast<double*>(base + o_de);
     L.sol = reinterpret_cast<sk_svm_solution*>(base + o_so);
+    L.info = reinterpret_cast<sk_svm_shrink_info*>(base + o_in);
     // largest class first: its workgroups run longest
     for (int c = sk::kSvmClasses - 1; c >= 0; --c) {
       if (which[c].empty()) continue;
       L.which = reinterpret_cast<const int32_t*>(base + o_wh) + which_off[c];
       const int grid = (int)which[c].size();
       SK_SVM_HIP(sk::lev_mark(ctx, S));
-      if (c == 0) SK_SVM_HIP(sk::launch_class<sk::kSvmThreads[0]>(L, grid, S));
-      if (c == 1) SK_SVM_HIP(sk::launch_class<sk::kSvmThreads[1]>(L, grid, S));
-      if (c == 2) SK_SVM_HIP(sk::launch_class<sk::kSvmThreads[2]>(L, grid, S));
+      if (c == 0) SK_SVM_HIP(sk::launch_class<sk::kSvmThreads[0]>(L, shrinking != 0, grid, S));
+      if (c == 1) SK_SVM_HIP(sk::launch_class<sk::kSvmThreads[1]>(L, shrinking != 0, grid, S));
+      if (c == 2) SK_SVM_HIP(sk::launch_class<sk::kSvmThreads[2]>(L, shrinking != 0, grid, S));
       SK_SVM_HIP(sk::lev_mark(ctx, S));
     }
     SK_SVM_HIP(hipMemcpyAsync(alpha_out, base + o_al, (size_t)sum_train * 8, hipMemcpyDeviceToHost, S));
@@ -525,10 +800,22 @@ extern "C" int sk_svm_train_batch(sk_context* ctx, const double* gram, int32_t n
       SK_SVM_HIP(hipMemcpyAsync(dec_out, base + o_de, (size_t)sum_test * 8, hipMemcpyDeviceToHost, S));
     SK_SVM_HIP(hipMemcpyAsync(solutions, base + o_so, (size_t)n_problems * sizeof(sk_svm_solution),
                               hipMemcpyDeviceToHost, S));
+    if (info && shrinking)
+      SK_SVM_HIP(hipMemcpyAsync(info, base + o_in, (size_t)n_problems * sizeof(sk_svm_shrink_info),
+                                hipMemcpyDeviceToHost, S));
     SK_SVM_HIP(hipStreamSynchronize(S));
     SK_SVM_HIP(sk::lev_collect(ctx));
+    if (info && !shrinking)
+      for (int p = 0; p < n_problems; ++p) info[p] = sk_svm_shrink_info{0, 0, problems[p].n_train, 0, 0, 0, 0};
     return SK_OK;
   } catch (const std::bad_alloc&) {
     return sk::ctx_fail(ctx, SK_ERR_ALLOC, "sk_svm_train_batch: host memory");
   }
+}
+
+extern "C" int sk_svm_train_batch(sk_context* ctx, const double* gram, int32_t n, const double* labels,
+                                  const sk_svm_problem* problems, int32_t n_problems, double* alpha_out,
+                                  double* dec_out, sk_svm_solution* solutions) {
+  return sk_svm_train_batch_ex(ctx, gram, n, labels, problems, n_problems, 0, alpha_out, dec_out, solutions,
+                               nullptr);
 }

@@ -223,30 +223,33 @@ def feature_gram_cross(test: FeatureSet, train: FeatureSet, kernel: _FeatureKern
 
 
 def feature_auc_objective(fs: FeatureSet, kernel: _FeatureKernel, n_folds: int, C: float, eps: float = 1e-3,
-                          max_iter=None, ctx=None, n_threads: int = 0):
+                          max_iter=None, ctx=None, n_threads: int = 0, shrinking: bool = False):
     """One step of Optimizer::optimize (optimizer/optimizer.cpp:45-77) for a
     feature-vector kernel: feature_gram, then svm.auc_objective over it.
-    Returns (f, g, records) with g over (C, the kernel's parameters)."""
+    Returns (f, g, records) with g over (C, the kernel's parameters).
+    shrinking=True trains as the reference's optimizer does."""
     from . import svm
     K, G = feature_gram(fs, kernel, ctx=ctx, n_threads=n_threads)
     return svm.auc_objective(K, G, fs.labels, n_folds, C, eps=eps, ctx=ctx, n_threads=n_threads,
-                             max_iter=svm.DEFAULT_MAX_ITER if max_iter is None else max_iter)
+                             max_iter=svm.DEFAULT_MAX_ITER if max_iter is None else max_iter, shrinking=shrinking)
 
 
 def optimize_features(fs: FeatureSet, kernel: _FeatureKernel, C: float = 1.0, n_folds: int = 10, ctx=None,
-                      eps: float = 1e-3, max_iter=None, n_threads: int = 0, callback=None, **options):
+                      eps: float = 1e-3, max_iter=None, n_threads: int = 0, callback=None, shrinking: bool = False,
+                      **options):
     """The reference's rbf / poly / sigmoid optimizer: minimise minus the
     cross-validated smoothed AUC over (C, the kernel's parameters) with
     svm.optimize, under the reference's bounds (C and gamma >= 1e-5, coef0
     unbounded).  callback(step, x, f, g) is called after every evaluation.
     Returns (result, kernel at the optimum); result.x[0] is C.  The iterates
-    are SciPy's L-BFGS-B's, not lbfgsb.c's (see svm.optimize)."""
+    are SciPy's L-BFGS-B's, not lbfgsb.c's (see svm.optimize).  shrinking=True
+    trains every fold with libsvm's shrinking, as the reference does."""
     from . import svm
     step = [0]
 
     def objective(x):
         f, g, _ = feature_auc_objective(fs, kernel.with_params(x[1:]), n_folds, float(x[0]), eps=eps,
-                                        max_iter=max_iter, ctx=ctx, n_threads=n_threads)
+                                        max_iter=max_iter, ctx=ctx, n_threads=n_threads, shrinking=shrinking)
         step[0] += 1
         if callback is not None:
             callback(step[0], np.array(x, dtype=np.float64), f, g)

@@ -787,22 +787,24 @@ class Context:
         return assemble_gradients(iu, ju, val, grad, n, normalize)
 
     def bpla_auc_objective(self, ds: Dataset, kernel: "BPLAKernel", labels, n_folds: int, C: float,
-                           normalize: bool = False, eps: float = 1e-3, max_iter=None):
+                           normalize: bool = False, eps: float = 1e-3, max_iter=None, shrinking: bool = False):
         """One step of the bpla_optimizer on this GPU: bpla_gradient_gram,
         then svm.auc_objective over it (optimizer/optimizer.cpp:45-77).
         Returns (f, g, records) with g over (C, alpha, beta, gap, ext)."""
         from . import svm
         K, G = self.bpla_gradient_gram(ds, kernel, normalize)
-        return svm.auc_objective(K, G, labels, n_folds, C, eps=eps, ctx=self,
+        return svm.auc_objective(K, G, labels, n_folds, C, eps=eps, ctx=self, shrinking=shrinking,
                                  max_iter=svm.DEFAULT_MAX_ITER if max_iter is None else max_iter)
 
-    def feature_auc_objective(self, fs, kernel, n_folds: int, C: float, eps: float = 1e-3, max_iter=None):
+    def feature_auc_objective(self, fs, kernel, n_folds: int, C: float, eps: float = 1e-3, max_iter=None,
+                              shrinking: bool = False):
         """One step of the rbf / poly / sigmoid optimizer on this GPU:
         features.feature_gram, then svm.auc_objective over it
         (optimizer/optimizer.cpp:45-77).  Returns (f, g, records) with g over
         (C, the kernel's parameters)."""
         from . import features
-        return features.feature_auc_objective(fs, kernel, n_folds, C, eps=eps, max_iter=max_iter, ctx=self)
+        return features.feature_auc_objective(fs, kernel, n_folds, C, eps=eps, max_iter=max_iter, ctx=self,
+                                              shrinking=shrinking)
 
     def comm_init(self, uid: bytes, rank: int, world: int) -> None:
         """This context's RCCL communicator (sk_comm_init); uid = the 128

@@ -8,7 +8,9 @@ with the reference's flags and defaults (-g 1, -c 1, -e 0.001, --factr 1e10,
 (optimizer/optimizer.cpp:43-85).  The iterates are SciPy's L-BFGS-B's, not
 lbfgsb.c's (svm.optimize): factr and pgtol map to SciPy's ftol = factr *
 machine epsilon and gtol.  --host runs every step on host threads instead of
-the GPU.
+the GPU.  --shrinking trains every fold with libsvm's shrinking, which the
+reference's optimizer hardcodes (optimizer/gradient.cpp:224); the default is
+without.
 """
 from __future__ import annotations
 
@@ -39,6 +41,8 @@ def parser() -> argparse.ArgumentParser:
     ap.add_argument("--nfold", "-v", type=int, default=10, help="n-fold cross validation mode")
     ap.add_argument("--host", action="store_true", help="run on host threads instead of the GPU")
     ap.add_argument("--device", type=int, default=0, help="GPU ordinal")
+    ap.add_argument("--shrinking", action="store_true",
+                    help="train with libsvm's shrinking heuristic, as the reference's optimizer does")
     ap.add_argument("--max-steps", type=int, default=None, help="stop after this many evaluations (SciPy's maxfun)")
     ap.add_argument("data", metavar="training-data")
     return ap
@@ -80,7 +84,8 @@ def main(argv=None) -> int:
     if a.max_steps is not None:
         options["maxfun"] = a.max_steps
     res, best = features.optimize_features(fs, make_kernel(a), C=a.cost, n_folds=a.nfold, ctx=ctx, eps=a.epsilon,
-                                           callback=functools.partial(print_step, n_folds=a.nfold), **options)
+                                           callback=functools.partial(print_step, n_folds=a.nfold),
+                                           shrinking=a.shrinking, **options)
     print("\nOptimized Parameters:")
     names = ", ".join(f"{k}={_g(v)}" for k, v in zip(best.names[:1], best.params[:1]))
     tail = "".join(f" {k}={_g(v)}" for k, v in zip(best.names[1:], best.params[1:]))

@@ -2,8 +2,9 @@
 replaces `svm-train -t 4` on the printed matrix and the per-fold solves of the
 reference's optimizer.  Many (training subset, C) problems over one Gram are
 solved in one call: on the GPU with a Context (one workgroup per problem), on
-host threads without one.  libsvm's SMO solver without shrinking; see
-include/stem_kernel.h for the arithmetic contract."""
+host threads without one.  libsvm's SMO solver, without shrinking by default
+and with it on request (shrinking=True: what `svm-train` and the reference's
+optimizer run); see include/stem_kernel.h for the arithmetic contract."""
 from __future__ import annotations
 
 import ctypes as C
@@ -39,10 +40,12 @@ class SVMSolution:
     """One solved problem: alpha (>= 0, in training order, not multiplied by
     y), rho, obj, iterations, status ("converged", "not converged" when
     max_iter was reached, "no working pair" for a Gram that is not finite),
-    n_free, n_bound, the decision values of the problem's test list, and the
-    problem's train, test, Cp and Cn."""
+    n_free, n_bound, the decision values of the problem's test list, the
+    problem's train, test, Cp and Cn, and shrink: sk_svm_shrink_info as a dict
+    (shrink_calls, shrunk_calls, min_active, unshrunk, regrown,
+    reconstructions, resumed; without shrinking min_active = l, zeros else)."""
 
-    def __init__(self, train, test, labels, alpha, decision, s, Cp=None, Cn=None):
+    def __init__(self, train, test, labels, alpha, decision, s, Cp=None, Cn=None, shrink=None):
         self.train, self.test, self.labels = train, test, labels
         self.Cp, self.Cn = Cp, Cn
         self.alpha, self.decision = alpha, decision
@@ -51,6 +54,7 @@ class SVMSolution:
         self.status = STATUS.get(int(s.status), str(int(s.status)))
         self.converged = int(s.status) == 0
         self.n_free, self.n_bound = int(s.n_free), int(s.n_bound)
+        self.shrink = None if shrink is None else {k: int(getattr(shrink, k)) for k, _ in shrink._fields_}
 
     def __repr__(self):
         return (f"SVMSolution(l={len(self.train)}, {self.status}, iterations={self.iterations}, "
@@ -85,13 +89,16 @@ def _problem(p, default_train):
             int(p.get("max_iter", DEFAULT_MAX_ITER)))
 
 
-def svm_train_batch(K, labels, problems: Sequence[dict], ctx=None, n_threads: int = 0):
+def svm_train_batch(K, labels, problems: Sequence[dict], ctx=None, n_threads: int = 0, shrinking: bool = False):
     """Solve every problem of `problems` over the Gram K (n x n) with the
     labels' signs as classes; returns one SVMSolution per problem.  A problem
     is a dict with train (indices into K, default all), test (indices whose
     decision values are wanted), C or Cp and Cn (default 1), eps (default
     1e-3) and max_iter (default DEFAULT_MAX_ITER).  ctx: a Context runs the
-    batch on its GPU; None runs it on n_threads host threads (0 = all)."""
+    batch on its GPU; None runs it on n_threads host threads (0 = all).
+    shrinking: run libsvm's solver with its shrinking heuristic (the whole
+    call; the reference's Solve(..., shrinking = 1) bit for bit) instead of
+    without (shrinking = 0, the default)."""
     K = np.ascontiguousarray(K, dtype=np.float64)
     if K.ndim != 2 or K.shape[0] != K.shape[1]:
         raise ValueError("K must be a square matrix")
@@ -112,22 +119,24 @@ def svm_train_batch(K, labels, problems: Sequence[dict], ctx=None, n_threads: in
     dec = np.zeros(max(int(doff[-1]), 1))
     sol = (SvmSolution * max(len(ps), 1))()
     args = (K.ctypes.data_as(_lib._F64P), n, labels.ctypes.data_as(_lib._F64P), arr, len(ps))
-    outs = (alpha.ctypes.data_as(_lib._F64P), dec.ctypes.data_as(_lib._F64P), sol)
+    info = (_lib.SvmShrinkInfo * max(len(ps), 1))()
+    outs = (alpha.ctypes.data_as(_lib._F64P), dec.ctypes.data_as(_lib._F64P), sol, info)
+    flag = 1 if shrinking else 0
     if ctx is None:
-        check(lib().sk_svm_train_batch_host(*args, int(n_threads), *outs))
+        check(lib().sk_svm_train_batch_host_ex(*args, int(n_threads), flag, *outs))
     else:
-        check(lib().sk_svm_train_batch(ctx.handle, *args, *outs), ctx.handle)
+        check(lib().sk_svm_train_batch_ex(ctx.handle, *args, flag, *outs), ctx.handle)
     return [SVMSolution(p[0], p[1], labels, alpha[aoff[k]:aoff[k + 1]].copy(), dec[doff[k]:doff[k + 1]].copy(),
-                        sol[k], p[2], p[3]) for k, p in enumerate(ps)]
+                        sol[k], p[2], p[3], info[k]) for k, p in enumerate(ps)]
 
 
 def svm_train(K, labels, C: float = 1.0, train=None, test=None, eps: float = 1e-3,
               max_iter: int = DEFAULT_MAX_ITER, Cp: Optional[float] = None, Cn: Optional[float] = None,
-              ctx=None) -> SVMSolution:
+              ctx=None, shrinking: bool = False) -> SVMSolution:
     """One C-SVC problem (svm_train_batch with a single entry)."""
     p = dict(train=train, test=test, Cp=C if Cp is None else Cp, Cn=C if Cn is None else Cn, eps=eps,
              max_iter=max_iter)
-    return svm_train_batch(K, labels, [p], ctx=ctx)[0]
+    return svm_train_batch(K, labels, [p], ctx=ctx, shrinking=shrinking)[0]
 
 
 def cv_split(n: int, n_folds: int, fold: int):
@@ -172,7 +181,7 @@ class CrossValidation:
 
 
 def cross_validate(K, labels, n_folds: int, Cs, eps: float = 1e-3, max_iter: int = DEFAULT_MAX_ITER,
-                   ctx=None, n_threads: int = 0) -> CrossValidation:
+                   ctx=None, n_threads: int = 0, shrinking: bool = False) -> CrossValidation:
     """n_folds-fold cross-validation for every C of Cs in one batch: the
     len(Cs) * n_folds problems of the reference's split.  ctx=None runs the
     host path."""
@@ -183,7 +192,7 @@ def cross_validate(K, labels, n_folds: int, Cs, eps: float = 1e-3, max_iter: int
     Cs = [float(c) for c in Cs]
     folds = [cv_split(n, n_folds, f) for f in range(n_folds)]
     ps = [dict(train=tr, test=ts, C=c, eps=eps, max_iter=max_iter) for c in Cs for tr, ts in folds]
-    flat = svm_train_batch(K, labels, ps, ctx=ctx, n_threads=n_threads)
+    flat = svm_train_batch(K, labels, ps, ctx=ctx, n_threads=n_threads, shrinking=shrinking)
     sols = [flat[k * n_folds:(k + 1) * n_folds] for k in range(len(Cs))]
     return CrossValidation(Cs, folds, sols, labels)
 
@@ -296,7 +305,7 @@ def auc_gradient_batch(K, G, labels, problems: Sequence[dict], ctx=None, n_threa
 
 
 def auc_objective(K, G, labels, n_folds: int, C: float, eps: float = 1e-3, max_iter: int = DEFAULT_MAX_ITER,
-                  ctx=None, n_threads: int = 0):
+                  ctx=None, n_threads: int = 0, shrinking: bool = False):
     """One optimizer step's objective and gradient (Optimizer::optimize,
     optimizer/optimizer.cpp:60-77): over the n_folds folds of cv_split, train
     with C (svm_train_batch with each fold's test list), form auc_delta of
@@ -304,14 +313,15 @@ def auc_objective(K, G, labels, n_folds: int, C: float, eps: float = 1e-3, max_i
     g[0] -= cg, g[1 + p] -= fg[p] in fold order.  Returns (f, g, records):
     minus the summed smoothed AUC, its gradient with respect to (C,
     parameters), and per fold a dict with f, delta, the SVMSolution and the
-    AUCGradient.  Training is without shrinking (see svm_train_batch)."""
+    AUCGradient.  Training is without shrinking unless shrinking=True, which
+    is how the reference's optimizer trains (optimizer/gradient.cpp:224)."""
     labels = np.ascontiguousarray(labels, dtype=np.float64).reshape(-1)
     n = len(labels)
     if not 2 <= n_folds <= n:
         raise ValueError("n_folds must be in [2, n]")
     folds = [cv_split(n, n_folds, f) for f in range(n_folds)]
     sols = svm_train_batch(K, labels, [dict(train=tr, test=ts, C=C, eps=eps, max_iter=max_iter)
-                                       for tr, ts in folds], ctx=ctx, n_threads=n_threads)
+                                       for tr, ts in folds], ctx=ctx, n_threads=n_threads, shrinking=shrinking)
     fd = [auc_delta(s.decision, labels[ts]) for s, (_, ts) in zip(sols, folds)]
     grads = auc_gradient_batch(K, G, labels, [dict(train=tr, test=ts, C=C, alpha=s.alpha, rho=s.rho, delta=d)
                                               for (tr, ts), s, (_, d) in zip(folds, sols, fd)],

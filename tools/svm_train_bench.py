@@ -20,7 +20,20 @@ running them one after another).  Iterations/s per card is the batch's total
 iterations over its GPU span.  The alphas of the two paths are compared bit
 for bit.  Writes one JSON document (--out).  For scale, the reference
 Solver's single-core time on one of these problems is what
-tools/make_golden_svm_train.py prints (DESIGN.md records it)."""
+tools/make_golden_svm_train.py prints (DESIGN.md records it).
+
+--shrinking measures the same 50 problems with libsvm's shrinking on
+(sk_svm_train_batch_ex) instead: GPU span and wall time of the batch, the
+iterations, what the shrinking did (sk_svm_shrink_info; per problem the
+smallest active size, and its minimum and mean over the batch), the host
+path's time, and GPU against host bit for bit; and once in the same process
+the batch with shrinking off.  --commit-runs and --parent-runs name JSON
+documents written by this tool without --shrinking on the same day, by this
+commit and by its parent commit: their median spans are recorded, with the
+parent's run-to-run spread (largest minus smallest), and whether shrinking
+off has become slower than the parent by more than that spread.  With --out
+the record goes under the key "shrinking" of that document, whose other keys
+are kept."""
 import argparse
 import json
 import os
@@ -45,12 +58,17 @@ def main():
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--max-iter", type=int, default=2_000_000)
     ap.add_argument("--out", default="")
+    ap.add_argument("--shrinking", action="store_true", help="measure the batch with shrinking on (see above)")
+    ap.add_argument("--commit-runs", nargs="*", default=[], help="JSON of runs without --shrinking, this commit")
+    ap.add_argument("--parent-runs", nargs="*", default=[], help="JSON of runs without --shrinking, parent commit")
     a = ap.parse_args()
     K, y = svm_ref.int_gram(0x5A17B001, a.n, 16, 4)
     Cs = [2.0 ** e for e in range(-6, 4)]
     folds = [svm_ref.split(a.n, a.folds, f) for f in range(a.folds)]
     ps = [dict(train=tr, test=ts, C=c, eps=1e-3, max_iter=a.max_iter) for c in Cs for tr, ts in folds]
     ctx = ska.Context(0)
+    if a.shrinking:
+        return shrinking_record(a, ctx, K, y, ps)
 
     wall, span = [], []
     for it in range(a.warmup + a.calls):
@@ -96,6 +114,79 @@ def main():
     )
     text = json.dumps(res, indent=1)
     print(text)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(text + "\n")
+
+
+def timed_batch(a, ctx, K, y, ps, **kw):
+    """(solutions, wall ms, span ms) of --calls calls after --warmup warm-ups."""
+    wall, span = [], []
+    for it in range(a.warmup + a.calls):
+        t0 = time.perf_counter()
+        sols = ska.svm_train_batch(K, y, ps, ctx=ctx, **kw)
+        t1 = time.perf_counter()
+        if it >= a.warmup:
+            wall.append((t1 - t0) * 1e3)
+            span.append(ctx.last_launch_ms()["ms_sum"])
+    return sols, wall, span
+
+
+def shrinking_record(a, ctx, K, y, ps):
+    off, off_wall, off_span = timed_batch(a, ctx, K, y, ps)
+    on, wall, span = timed_batch(a, ctx, K, y, ps, shrinking=True)
+    hwall = []
+    for it in range(1 + a.calls):
+        t0 = time.perf_counter()
+        host = ska.svm_train_batch(K, y, ps, n_threads=a.threads, shrinking=True)
+        t1 = time.perf_counter()
+        if it >= 1:
+            hwall.append((t1 - t0) * 1e3)
+    same = all(np.array_equal(g.alpha.view(np.int64), h.alpha.view(np.int64)) and g.iterations == h.iterations and
+               (g.rho, g.obj) == (h.rho, h.obj) and g.shrink == h.shrink for g, h in zip(on, host))
+    iters, iters_off = [s.iterations for s in on], [s.iterations for s in off]
+    min_active = [s.shrink["min_active"] for s in on]
+    rec = dict(
+        problems=len(ps), calls=a.calls, warmup=a.warmup, host_threads=a.threads,
+        iterations=iters, total_iterations=int(sum(iters)), total_iterations_shrinking_off=int(sum(iters_off)),
+        all_converged=all(s.converged for s in on), bit_equal_gpu_host=bool(same),
+        gpu_batch_wall_ms=wall, gpu_batch_span_ms=span, host_batch_wall_ms=hwall,
+        median_gpu_batch_wall_ms=statistics.median(wall), median_gpu_batch_span_ms=statistics.median(span),
+        median_host_batch_wall_ms=statistics.median(hwall),
+        us_per_iteration_longest_problem=statistics.median(span) * 1e3 / max(iters),
+        same_process_shrinking_off=dict(gpu_batch_span_ms=off_span, median_gpu_batch_span_ms=statistics.median(off_span),
+                                        us_per_iteration_longest_problem=statistics.median(off_span) * 1e3 / max(iters_off)),
+        min_active_per_problem=min_active, min_active_min=min(min_active), min_active_mean=float(np.mean(min_active)),
+        n_train=sorted({len(p["train"]) for p in ps}),
+        shrink_calls=[s.shrink["shrink_calls"] for s in on], shrunk_calls=[s.shrink["shrunk_calls"] for s in on],
+        unshrunk=int(sum(s.shrink["unshrunk"] for s in on)), regrown=int(sum(s.shrink["regrown"] for s in on)),
+        reconstructions=int(sum(s.shrink["reconstructions"] for s in on)),
+        resumed=int(sum(s.shrink["resumed"] for s in on)),
+        alphas_differ_from_shrinking_off=int(sum(not np.array_equal(g.alpha, o.alpha) for g, o in zip(on, off))),
+    )
+
+    def spans(paths):
+        out = []
+        for path in paths:
+            with open(path) as f:
+                out.append(json.load(f)["median_gpu_batch_span_ms"])
+        return out
+
+    if a.commit_runs and a.parent_runs:
+        mine, parent = spans(a.commit_runs), spans(a.parent_runs)
+        spread = max(parent) - min(parent)
+        rec["shrinking_off_same_day"] = dict(
+            what="median GPU span of the batch without shrinking, one entry per run of this tool",
+            this_commit_span_ms=mine, parent_commit_span_ms=parent, parent_spread_ms=spread,
+            this_commit_median_ms=statistics.median(mine), parent_median_ms=statistics.median(parent),
+            slower_than_parent_by_more_than_the_spread=bool(statistics.median(mine) - statistics.median(parent) > spread))
+    doc = {}
+    if a.out and os.path.exists(a.out):
+        with open(a.out) as f:
+            doc = json.load(f)
+    doc["shrinking"] = rec
+    text = json.dumps(doc if a.out else rec, indent=1)
+    print(json.dumps(rec, indent=1))
     if a.out:
         with open(a.out, "w") as f:
             f.write(text + "\n")
