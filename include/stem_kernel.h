@@ -678,6 +678,111 @@ int sk_svm_train_shape(int32_t *bounds, int32_t *n_classes, int32_t *max_train);
 int sk_svm_model_write(const char *path, const double *labels, int32_t n, const int32_t *train,
                        int32_t n_train, const double *alpha, double rho);
 
+/* ------------------------------------------- SVM training: the five formulations
+ * svm_train_one (libsvm/svm.cpp:245-300) whole: next to C-SVC the batch
+ * solves nu-SVC, one-class, epsilon-SVR and nu-SVR tasks over one Gram, what
+ * `svm-train -s 1|2|3|4 -t 4` does on the printed matrix.  WITHOUT SHRINKING:
+ * every task is the reference's Solve(..., shrinking = 0) bit for bit;
+ * shrinking for the four new types (Solver_NU::do_shrinking included) is not
+ * built, and the calls below carry no shrinking flag.
+ *
+ * Per type, as the reference's solve_* functions set the problem up
+ * (svm.cpp:38-234), l = n_train, target_k the target of training example k:
+ *   C_SVC        solve_c_svc: sk_svm_train_batch's problem with Cp = Cn = C.
+ *   NU_SVC       solve_nu_svc (:73-126): y = sign of the target, p = 0,
+ *                bounds 1, the start point alpha_k = min(1, sum) with sum
+ *                running down from nu l / 2 per class in list order;
+ *                Solver_NU; then alpha_k *= y_k / r, rho /= r, obj /= r r.
+ *   ONE_CLASS    solve_one_class (:128-158): y = +1, p = 0, bounds 1, the
+ *                first (int)(nu l) alphas 1, the next nu l - (int)(nu l).
+ *                Targets are not read.
+ *   EPSILON_SVR  solve_epsilon_svr (:160-196): 2 l positions, position k and
+ *                k + l both example k with y = +1 and -1 (SVR_Q,
+ *                libsvm/qmatrix.cpp:423-475, QD duplicated :438-439), linear
+ *                term p - target and p + target, alpha = 0, bounds C.
+ *   NU_SVR       solve_nu_svr (:198-234): the same positions, linear term
+ *                -target and +target, alpha_k = alpha_{k+l} = min(sum, C) with
+ *                sum running down from C nu l / 2 in list order; Solver_NU.
+ * Q_i[k] = y_i y_k (float)K[t_i][t_k] over positions (the three Q classes of
+ * qmatrix.cpp give this value), K read by row only.  The general Solve
+ * (solver.cpp:81-349): G = p, then G[j] += alpha_i Q_i[j] for every i not at
+ * its lower bound in ascending order, a multiply and an add (:113-135); obj =
+ * sum alpha (G + p) / 2 (:314-321).  Solver_NU: per-class working-set
+ * selection (:595-705; >= and <=, the last index wins, quad_coef in float, i
+ * from the class of the chosen j, stop on max(Gmaxp + Gmaxp2, Gmaxn + Gmaxn2)
+ * < eps; where the reference would index with -1 because no j exists the
+ * status is SK_SVM_NO_PAIR) and the two-sided calculate_rho (:799-848), which
+ * also gives r.
+ *
+ * coef_out (n_train per task, concatenated) is what svm_train_one leaves in
+ * alpha and what goes into a model's sv_coef: alpha y (C_SVC), alpha (y / r)
+ * (NU_SVC), alpha (ONE_CLASS), alpha_k - alpha_{k+l} (both SVR types).  rho
+ * and obj are what leaves svm_train_one (NU_SVC: divided by r and r r); r is
+ * Solver_NU's si->r as solved, 0 for the plain solver.  n_free and n_bound
+ * count the solver's positions (2 l of them for SVR).  Decision values of the
+ * test list: sum over coef_a != 0 of coef_a K[s][t_a], minus rho
+ * (svm_predict_values, svm.cpp:1053-1070); the host path sums in list order.
+ * The GPU path and the host path give the same coef, rho, obj, r, iterations,
+ * status and counts, bit for bit. */
+typedef enum {
+  SK_SVM_C_SVC = 0,
+  SK_SVM_NU_SVC = 1,
+  SK_SVM_ONE_CLASS = 2,
+  SK_SVM_EPSILON_SVR = 3,
+  SK_SVM_NU_SVR = 4
+} sk_svm_type;
+typedef struct {
+  const int32_t *train; /* indices into the Gram, in training order */
+  int32_t n_train;
+  const int32_t *test;  /* examples to evaluate after the solve (may be NULL) */
+  int32_t n_test;
+  int32_t svm_type;     /* sk_svm_type */
+  double C;             /* C_SVC, EPSILON_SVR, NU_SVR */
+  double nu;            /* NU_SVC, ONE_CLASS, NU_SVR */
+  double p;             /* EPSILON_SVR */
+  double eps;
+  int64_t max_iter;     /* mandatory, as in sk_svm_problem */
+} sk_svm_task;
+typedef struct {
+  double rho, obj;
+  int64_t iterations;
+  int32_t status;  /* sk_svm_status */
+  int32_t n_free;  /* positions with 0 < alpha < bound */
+  int32_t n_bound; /* positions at the upper bound */
+  double r;        /* Solver_NU's si->r; 0 for C_SVC, ONE_CLASS, EPSILON_SVR */
+} sk_svm_task_solution;
+/* targets: n values (class labels for the classifiers, by sign; real values
+ * for the SVR types; may be NULL when every task is ONE_CLASS).  Tasks of
+ * different types may share a call.  SK_ERR_INVALID, with nothing launched
+ * (svm_check_parameter, svm.cpp:1499-1615): an unknown svm_type; nu outside
+ * (0, 1] for the three nu types; NU_SVC with nu (n+ + n-) / 2 > min(n+, n-)
+ * (:1563-1610) or a classifier with one class only; C <= 0 where C is used;
+ * p < 0 for EPSILON_SVR; eps <= 0; max_iter < 1; n_train < 2; an index outside
+ * [0, n); an SVR target that is not finite.  SK_ERR_UNSUPPORTED, with nothing
+ * launched: a training list longer than sk_svm_solve_shape reports for its
+ * type (the GPU call only).  One kernel launch per (solver family, size class)
+ * in use, the families being C_SVC, the plain general solver (ONE_CLASS,
+ * EPSILON_SVR) and Solver_NU (NU_SVC, NU_SVR). */
+int sk_svm_solve_batch(sk_context *ctx, const double *gram, int32_t n, const double *targets,
+                       const sk_svm_task *tasks, int32_t n_tasks, double *coef_out, double *dec_out,
+                       sk_svm_task_solution *solutions);
+int sk_svm_solve_batch_host(const double *gram, int32_t n, const double *targets, const sk_svm_task *tasks,
+                            int32_t n_tasks, int32_t n_threads, double *coef_out, double *dec_out,
+                            sk_svm_task_solution *solutions);
+/* max_train[t], t an sk_svm_type (5 entries): the longest training list the
+ * GPU solver takes.  sk_svm_train_shape's max_train for C_SVC, NU_SVC and
+ * ONE_CLASS; half of it for the SVR types, whose 2 l positions share the
+ * kernel's position capacity (size classes go by positions). */
+int sk_svm_solve_shape(int32_t *max_train);
+/* svm_save_model's text (svm.cpp:1201-1286) for any svm_type, from coef as
+ * sk_svm_solve_batch returns it; sk_svm_model_load reads it back.  C_SVC and
+ * NU_SVC: as sk_svm_model_write (classes by first appearance, signs turned
+ * when the first training label is not > 0).  ONE_CLASS and the SVR types:
+ * nr_class 2, no label and nr_sv lines, the support vectors where
+ * fabs(coef) > 0 in list order (svm.cpp:677-717); targets may be NULL. */
+int sk_svm_model_write_ex(const char *path, int32_t svm_type, const double *targets, int32_t n,
+                          const int32_t *train, int32_t n_train, const double *coef, double rho);
+
 /* ------------------------------------------------- cross-validated AUC gradient
  * Steps 3 to 5 of GradientComputation::compute (optimizer/gradient.cpp:107-156)
  * for many (fold, C) problems over one Gram K and its derivative matrices

@@ -11,7 +11,7 @@ from .kernel_matrix import (  # noqa: F401
 from .svm import (  # noqa: F401
     DEFAULT_MAX_ITER, AUCGradient, CrossValidation, SVMSolution, auc_delta, auc_gradient_batch,
     auc_gradient_shape, auc_objective, cross_validate, cv_split, optimize, svm_train, svm_train_batch,
-    svm_train_shape,
+    svm_solve_shape, svm_train_shape,
 )
 
 from .features import (  # noqa: F401

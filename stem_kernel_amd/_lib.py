@@ -64,6 +64,17 @@ class SvmShrinkInfo(C.Structure):  # sk_svm_shrink_info
                                          "reconstructions", "resumed")]
 
 
+class SvmTask(C.Structure):  # sk_svm_task
+    _fields_ = [("train", C.POINTER(C.c_int32)), ("n_train", C.c_int32), ("test", C.POINTER(C.c_int32)),
+                ("n_test", C.c_int32), ("svm_type", C.c_int32), ("C", C.c_double), ("nu", C.c_double),
+                ("p", C.c_double), ("eps", C.c_double), ("max_iter", C.c_int64)]
+
+
+class SvmTaskSolution(C.Structure):  # sk_svm_task_solution
+    _fields_ = [("rho", C.c_double), ("obj", C.c_double), ("iterations", C.c_int64), ("status", C.c_int32),
+                ("n_free", C.c_int32), ("n_bound", C.c_int32), ("r", C.c_double)]
+
+
 class AucInfo(C.Structure):  # sk_auc_info
     _fields_ = [("n_free", C.c_int32), ("n_bound", C.c_int32), ("cg_iterations", C.c_int32),
                 ("finite", C.c_int32)]
@@ -192,6 +203,13 @@ SIGNATURES = {
                                              C.POINTER(SvmShrinkInfo)]),
     "sk_svm_train_shape": (C.c_int, [_I32P, _I32P, _I32P]),
     "sk_svm_model_write": (C.c_int, [C.c_char_p, _F64P, C.c_int32, _I32P, C.c_int32, _F64P, C.c_double]),
+    "sk_svm_solve_batch": (C.c_int, [_P, _F64P, C.c_int32, _F64P, C.POINTER(SvmTask), C.c_int32, _F64P, _F64P,
+                                     C.POINTER(SvmTaskSolution)]),
+    "sk_svm_solve_batch_host": (C.c_int, [_F64P, C.c_int32, _F64P, C.POINTER(SvmTask), C.c_int32, C.c_int32,
+                                          _F64P, _F64P, C.POINTER(SvmTaskSolution)]),
+    "sk_svm_solve_shape": (C.c_int, [_I32P]),
+    "sk_svm_model_write_ex": (C.c_int, [C.c_char_p, C.c_int32, _F64P, C.c_int32, _I32P, C.c_int32, _F64P,
+                                        C.c_double]),
     "sk_auc_delta": (C.c_int, [_F64P, _F64P, C.c_int32, _F64P, _F64P]),
     "sk_auc_gradient_batch": (C.c_int, [_P, _F64P, _F64P, C.c_int32, C.c_int32, _F64P, C.POINTER(AucProblem),
                                         C.c_int32, _F64P, _F64P, _F64P, C.POINTER(AucInfo)]),

@@ -25,6 +25,8 @@ from ._lib import SvmProblem, SvmSolution, check, lib
 # of libsvm's later releases) would be a kernel of 80 s.
 DEFAULT_MAX_ITER = 1_000_000
 STATUS = {0: "converged", 1: "not converged", 2: "no working pair"}
+# sk_svm_type, libsvm's numbering
+SVM_TYPES = {"c_svc": 0, "nu_svc": 1, "one_class": 2, "epsilon_svr": 3, "nu_svr": 4}
 
 
 def svm_train_shape() -> dict:
@@ -36,6 +38,15 @@ def svm_train_shape() -> dict:
     return {"bounds": [int(b[c]) for c in range(nc.value)], "max_train": mx.value}
 
 
+def svm_solve_shape() -> dict:
+    """The longest training list the GPU solver takes per svm_type
+    (sk_svm_solve_shape): svm_train_shape's max_train, and half of it for the
+    SVR types, whose 2 l positions go by svm_train_shape's bounds."""
+    m = (C.c_int32 * 5)()
+    check(lib().sk_svm_solve_shape(m))
+    return {name: int(m[t]) for name, t in SVM_TYPES.items()}
+
+
 class SVMSolution:
     """One solved problem: alpha (>= 0, in training order, not multiplied by
     y), rho, obj, iterations, status ("converged", "not converged" when
@@ -43,11 +54,25 @@ class SVMSolution:
     n_free, n_bound, the decision values of the problem's test list, the
     problem's train, test, Cp and Cn, and shrink: sk_svm_shrink_info as a dict
     (shrink_calls, shrunk_calls, min_active, unshrunk, regrown,
-    reconstructions, resumed; without shrinking min_active = l, zeros else)."""
+    reconstructions, resumed; without shrinking min_active = l, zeros else).
 
-    def __init__(self, train, test, labels, alpha, decision, s, Cp=None, Cn=None, shrink=None):
+    A problem solved with an svm_type (sk_svm_solve_batch) has svm_type, coef
+    (what goes into a model's sv_coef: alpha y, alpha y / r, alpha, or alpha -
+    alpha* by type), r (Solver_NU's, 0 for the plain solver), C, nu and p;
+    rho and obj are what svm_train_one leaves; n_free and n_bound count the
+    solver's positions (2 l for the SVR types); labels holds the targets;
+    alpha is None unless the type is c_svc (coef * y) or one_class (coef).
+    Without an svm_type: svm_type "c_svc", coef = alpha y, r = 0."""
+
+    def __init__(self, train, test, labels, alpha, decision, s, Cp=None, Cn=None, shrink=None, svm_type="c_svc",
+                 coef=None, nu=None, p=None):
         self.train, self.test, self.labels = train, test, labels
         self.Cp, self.Cn = Cp, Cn
+        self.svm_type, self.nu, self.p = svm_type, nu, p
+        self.r = float(getattr(s, "r", 0.0))
+        if coef is None:
+            coef = alpha * np.where(np.asarray(labels)[train] > 0, 1.0, -1.0)
+        self.coef = coef
         self.alpha, self.decision = alpha, decision
         self.rho, self.obj = float(s.rho), float(s.obj)
         self.iterations = int(s.iterations)
@@ -61,12 +86,20 @@ class SVMSolution:
                 f"rho={self.rho:.6g}, obj={self.obj:.6g}, n_free={self.n_free}, n_bound={self.n_bound})")
 
     def save(self, path: str) -> None:
-        """The model in svm_save_model's text format (sk_svm_model_write);
-        SVMModel(path) reads it back."""
+        """The model in svm_save_model's text format, of the solution's
+        svm_type (sk_svm_model_write, sk_svm_model_write_ex); SVMModel(path)
+        reads it back."""
         lab = np.ascontiguousarray(self.labels, dtype=np.float64)
-        check(lib().sk_svm_model_write(str(path).encode(), lab.ctypes.data_as(_lib._F64P), len(lab),
-                                       self.train.ctypes.data_as(_lib._I32P), len(self.train),
-                                       self.alpha.ctypes.data_as(_lib._F64P), self.rho))
+        ty = SVM_TYPES[getattr(self, "svm_type", "c_svc")]
+        if ty == 0 and self.alpha is not None:
+            check(lib().sk_svm_model_write(str(path).encode(), lab.ctypes.data_as(_lib._F64P), len(lab),
+                                           self.train.ctypes.data_as(_lib._I32P), len(self.train),
+                                           self.alpha.ctypes.data_as(_lib._F64P), self.rho))
+            return
+        coef = np.ascontiguousarray(self.coef, dtype=np.float64)
+        check(lib().sk_svm_model_write_ex(str(path).encode(), ty, lab.ctypes.data_as(_lib._F64P), len(lab),
+                                          self.train.ctypes.data_as(_lib._I32P), len(self.train),
+                                          coef.ctypes.data_as(_lib._F64P), self.rho))
 
     def model(self, path: str):
         """save(path), loaded as an SVMModel."""
@@ -77,8 +110,8 @@ class SVMSolution:
 
 def _problem(p, default_train):
     if not isinstance(p, dict):
-        raise TypeError("a problem is a dict: train, test, C or Cp/Cn, eps, max_iter")
-    unknown = set(p) - {"train", "test", "C", "Cp", "Cn", "eps", "max_iter"}
+        raise TypeError("a problem is a dict: train, test, C or Cp/Cn, eps, max_iter, svm_type, nu, p")
+    unknown = set(p) - {"train", "test", "C", "Cp", "Cn", "eps", "max_iter", "svm_type", "nu", "p"}
     if unknown:
         raise TypeError(f"unknown problem keys {sorted(unknown)}")
     train = default_train if p.get("train") is None else p["train"]
@@ -87,6 +120,43 @@ def _problem(p, default_train):
     c = float(p.get("C", 1.0))
     return (train, test, float(p.get("Cp", c)), float(p.get("Cn", c)), float(p.get("eps", 1e-3)),
             int(p.get("max_iter", DEFAULT_MAX_ITER)))
+
+
+def _solve_tasks(K, n, labels, problems, every, ctx, n_threads):
+    """The problems that name an svm_type: sk_svm_solve_batch[_host]."""
+    ps = []
+    for p in problems:
+        train, test, _, _, eps, mi = _problem(p, every)
+        if ("Cp" in p or "Cn" in p) and p["svm_type"] != "c_svc":
+            raise ValueError("Cp and Cn belong to c_svc; the other types take C")
+        if p["svm_type"] == "c_svc" and p.get("Cp", p.get("C", 1.0)) != p.get("Cn", p.get("C", 1.0)):
+            raise ValueError("a c_svc problem with svm_type takes one C; leave svm_type out for Cp != Cn")
+        c = float(p.get("C", p.get("Cp", 1.0)))
+        ps.append((train, test, SVM_TYPES[p["svm_type"]], c, float(p.get("nu", 0.5)), float(p.get("p", 0.1)), eps,
+                   mi, p["svm_type"]))
+    arr = (_lib.SvmTask * max(len(ps), 1))()
+    for a, (train, test, ty, c, nu, tube, eps, mi, _) in zip(arr, ps):
+        a.train, a.n_train = train.ctypes.data_as(_lib._I32P), len(train)
+        a.test, a.n_test = (test.ctypes.data_as(_lib._I32P) if len(test) else None), len(test)
+        a.svm_type, a.C, a.nu, a.p, a.eps, a.max_iter = ty, c, nu, tube, eps, mi
+    aoff = np.concatenate([[0], np.cumsum([len(p[0]) for p in ps])]).astype(np.int64)
+    doff = np.concatenate([[0], np.cumsum([len(p[1]) for p in ps])]).astype(np.int64)
+    coef = np.zeros(max(int(aoff[-1]), 1))
+    dec = np.zeros(max(int(doff[-1]), 1))
+    sol = (_lib.SvmTaskSolution * max(len(ps), 1))()
+    args = (K.ctypes.data_as(_lib._F64P), n, labels.ctypes.data_as(_lib._F64P), arr, len(ps))
+    outs = (coef.ctypes.data_as(_lib._F64P), dec.ctypes.data_as(_lib._F64P), sol)
+    if ctx is None:
+        check(lib().sk_svm_solve_batch_host(*args, int(n_threads), *outs))
+    else:
+        check(lib().sk_svm_solve_batch(ctx.handle, *args, *outs), ctx.handle)
+    res = []
+    for k, (train, test, ty, c, nu, tube, _, _, name) in enumerate(ps):
+        cf = coef[aoff[k]:aoff[k + 1]].copy()
+        alpha = cf * np.where(labels[train] > 0, 1.0, -1.0) if ty == 0 else cf if ty == 2 else None
+        res.append(SVMSolution(train, test, labels, alpha, dec[doff[k]:doff[k + 1]].copy(), sol[k], c, c,
+                               svm_type=name, coef=cf, nu=nu, p=tube))
+    return res
 
 
 def svm_train_batch(K, labels, problems: Sequence[dict], ctx=None, n_threads: int = 0, shrinking: bool = False):
@@ -98,7 +168,16 @@ def svm_train_batch(K, labels, problems: Sequence[dict], ctx=None, n_threads: in
     batch on its GPU; None runs it on n_threads host threads (0 = all).
     shrinking: run libsvm's solver with its shrinking heuristic (the whole
     call; the reference's Solve(..., shrinking = 1) bit for bit) instead of
-    without (shrinking = 0, the default)."""
+    without (shrinking = 0, the default).
+
+    A problem may name an svm_type ("c_svc", "nu_svc", "one_class",
+    "epsilon_svr", "nu_svr": svm_train_one, libsvm/svm.cpp:245-300) with nu
+    (default 0.5) and p (default 0.1, epsilon_svr's tube); then every problem
+    of the call has to name one, `labels` holds class labels for the
+    classifiers and real targets for the SVR types, and the batch goes through
+    sk_svm_solve_batch.  Those types are solved without shrinking only:
+    shrinking=True with a type other than c_svc is refused.  Problems without
+    svm_type go through sk_svm_train_batch as before."""
     K = np.ascontiguousarray(K, dtype=np.float64)
     if K.ndim != 2 or K.shape[0] != K.shape[1]:
         raise ValueError("K must be a square matrix")
@@ -107,6 +186,20 @@ def svm_train_batch(K, labels, problems: Sequence[dict], ctx=None, n_threads: in
     if len(labels) != n:
         raise ValueError("one label per row of K")
     every = np.arange(n, dtype=np.int32)
+    typed = [isinstance(p, dict) and p.get("svm_type") is not None for p in problems]
+    if any(typed):
+        if not all(typed):
+            raise ValueError("either every problem of a call names an svm_type or none does")
+        for p in problems:
+            if p["svm_type"] not in SVM_TYPES:
+                raise ValueError(f"svm_type {p['svm_type']!r}: one of {sorted(SVM_TYPES)}")
+        others = sorted({p["svm_type"] for p in problems} - {"c_svc"})
+        if shrinking and others:
+            raise ValueError(f"shrinking=True is built for c_svc only, not for {', '.join(others)}: "
+                             "solve those with shrinking=False")
+        if not shrinking:
+            return _solve_tasks(K, n, labels, problems, every, ctx, n_threads)
+        problems = [{k: v for k, v in p.items() if k not in ("svm_type", "nu", "p")} for p in problems]
     ps = [_problem(p, every) for p in problems]
     arr = (SvmProblem * max(len(ps), 1))()
     for a, (train, test, cp, cn, eps, mi) in zip(arr, ps):
@@ -132,8 +225,17 @@ def svm_train_batch(K, labels, problems: Sequence[dict], ctx=None, n_threads: in
 
 def svm_train(K, labels, C: float = 1.0, train=None, test=None, eps: float = 1e-3,
               max_iter: int = DEFAULT_MAX_ITER, Cp: Optional[float] = None, Cn: Optional[float] = None,
-              ctx=None, shrinking: bool = False) -> SVMSolution:
-    """One C-SVC problem (svm_train_batch with a single entry)."""
+              ctx=None, shrinking: bool = False, svm_type: Optional[str] = None, nu: float = 0.5,
+              p: float = 0.1) -> SVMSolution:
+    """One problem (svm_train_batch with a single entry): C-SVC, or with
+    svm_type one of the five formulations with nu and p."""
+    if svm_type is not None:
+        q = dict(train=train, test=test, C=C, eps=eps, max_iter=max_iter, svm_type=svm_type, nu=nu, p=p)
+        if Cp is not None:
+            q["Cp"] = Cp
+        if Cn is not None:
+            q["Cn"] = Cn
+        return svm_train_batch(K, labels, [q], ctx=ctx, shrinking=shrinking)[0]
     p = dict(train=train, test=test, Cp=C if Cp is None else Cp, Cn=C if Cn is None else Cn, eps=eps,
              max_iter=max_iter)
     return svm_train_batch(K, labels, [p], ctx=ctx, shrinking=shrinking)[0]
