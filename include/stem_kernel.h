@@ -256,6 +256,14 @@ int sk_dataset_shape(const sk_dataset *ds, int i, int32_t *n_nodes,
 int sk_dataset_row_traffic(const sk_dataset *ds, int i, int32_t *rows, int32_t *stored,
                            int32_t *slab_reads, int32_t *gamma_reads, int32_t *phi_reads,
                            int32_t *reg_reads, int32_t *y_slots);
+/* Shared child sums of example i in the x role: the
+ * shared-sum combination rows the factored gamma schedule adds for it and the
+ * child records of its rows they replaced; both 0 where the dataset runs the
+ * plain gamma schedule.  sk_dataset_row_traffic counts the schedule that
+ * runs.  No counterpart in the reference.  The dataset must be uploaded
+ * (packed). */
+int sk_dataset_shared_sums(const sk_dataset *ds, int i, int32_t *shared_rows,
+                           int32_t *member_records);
 /* DAG arrays of example i (packer-parity introspection; any pointer may be
  * NULL).  Node arrays have n_nodes entries, edge arrays n_edges (node-major,
  * reference list order), bp arrays n_bpfreq. */

@@ -464,26 +464,40 @@ int sk_dataset_row_traffic(const sk_dataset* ds, int i, int32_t* rows, int32_t* 
   // previous row's (taken from registers); stored rows (slot < 0x4000)
   int32_t st = 0, sl = 0, ga = 0, ph = 0, rg = 0;
   uint32_t prev = 0xffffu;
-  size_t k = (size_t)P.ex_xgch_base[i];
-  for (size_t r = (size_t)P.ex_xg_base[i]; r < (size_t)P.ex_xg_base[i] + P.ex_nlxg[i]; ++r) {
-    const int ne = P.xgrow[r].a & 0xff;
+  // (of the schedule the kernel runs: the factored one where it was built)
+  const auto& rows_ = P.run_rows();
+  const auto& ch_ = P.run_ch();
+  const int32_t nlr = P.run_nl()[i];
+  size_t k = (size_t)P.run_ch_base()[i];
+  for (size_t r = (size_t)P.run_base()[i]; r < (size_t)P.run_base()[i] + nlr; ++r) {
+    const int ne = rows_[r].a & 0xff;
     for (int t = 0; t < ne; ++t, ++k) {
-      const uint32_t c = P.xg_ch[k] & 0xffffu;
+      const uint32_t c = ch_[k] & 0xffffu;
       if (c == prev) ++rg;
       else if (c & 0x8000u) ++ga;
       else if (c & 0x4000u) ++ph;
       else ++sl;
     }
-    prev = P.xgrow[r].b >> 16;
+    prev = rows_[r].b >> 16;
     st += prev < 0x4000u;
   }
-  if (rows) *rows = P.ex_nlxg[i];
+  if (rows) *rows = nlr;
   if (stored) *stored = st;
   if (slab_reads) *slab_reads = sl;
   if (gamma_reads) *gamma_reads = ga;
   if (phi_reads) *phi_reads = ph;
   if (reg_reads) *reg_reads = rg;
   if (y_slots) *y_slots = P.ex_nl[i];
+  return SK_OK;
+}
+
+int sk_dataset_shared_sums(const sk_dataset* ds, int i, int32_t* shared_rows, int32_t* member_records) {
+  if (!ds) return SK_ERR_INVALID;
+  if (i < 0 || i >= (int)ds->ex.size()) return SK_ERR_RANGE;
+  const sk::HostPack& P = ds->pack;
+  if ((int)P.ex_nlxg.size() != (int)ds->ex.size()) return SK_ERR_INVALID;  // not packed yet
+  if (shared_rows) *shared_rows = P.shared_sums ? P.ex_ss_rows[i] : 0;
+  if (member_records) *member_records = P.shared_sums ? P.ex_ss_repl[i] : 0;
   return SK_OK;
 }
 

@@ -21,6 +21,7 @@
 #include <utility>
 #include <vector>
 
+#include "host/pack_shared_sums.h"
 #include "host/runtime_types.h"
 
 namespace sk {
@@ -216,6 +217,10 @@ struct KeyTables {
   std::vector<uint32_t> gam_key;  // (empty unless gam_on)
   std::vector<uint64_t> phi_raw;  // child gamma key:32 | code:16 | len:16 (sorted: by child key)
   bool gam_on = false, phi_on = false;
+  // the factored gamma schedule (shared child sums, pack_shared_sums.cpp)
+  // and its group-value threshold
+  bool ss_on = false;
+  int ss_thr = 0;
   uint32_t gamma_idx(uint32_t key) const {
     return (uint32_t)(std::lower_bound(gam_key.begin(), gam_key.end(), key) - gam_key.begin());
   }
@@ -267,6 +272,8 @@ KeyTables key_tables(const std::vector<Example>& ex, int nthr) {
   std::sort(K.phi_raw.begin(), K.phi_raw.end());
   K.phi_raw.erase(std::unique(K.phi_raw.begin(), K.phi_raw.end()), K.phi_raw.end());
   K.phi_on = K.gam_on && !K.phi_raw.empty() && K.phi_raw.size() < 0x4000 && !SK_KNOB("SK_NO_PHI");
+  K.ss_on = K.gam_on && !SK_KNOB("SK_NO_SHARED_SUMS");
+  if (const char* t = SK_KNOB("SK_SHARED_SUMS_THR")) K.ss_thr = std::atoi(t);
   return K;
 }
 
@@ -451,6 +458,12 @@ struct XOut {
   std::vector<sk::XRow> xrow, xgrow;
   std::vector<float4> pos_prof, pos_lru;
   std::vector<uint64_t> ex_phi_bits;
+  // the factored gamma schedule (empty unless K.ss_on)
+  std::vector<sk::XRow> xf_row;
+  std::vector<uint32_t> xf_node, xf_ch, xf_clg, xf_gra_row;
+  std::vector<float> xf_cpf;
+  std::vector<uint8_t> xf_cty;
+  int ss_rows = 0, ss_repl = 0;
   int nl = 0, nlev = 0, max_slots = 0, n_nostore = 0, n_nodes = 0, gslots = 0;
   bool big = false;
   int rc = SK_OK;
@@ -774,6 +787,12 @@ void pack_x(const Example& X, const KeyTables& K, XOut& O) {
           if (X.edge_to[k] == v) nostore[v] = 1;
       }
     }
+    // the same rows as the input of the factored schedule
+    std::vector<sk::SsRow> ss_in;
+    std::vector<int32_t> grow_of(nn, -1);
+    std::vector<uint32_t> ss_gra;  // the phi rows, by input row
+    if (K.ss_on) ss_in.reserve(order.size());
+    uint32_t ss_key = (uint32_t)nn;  // identities of the phi rows' components (never shared)
     for (int v : order) {
       const uint32_t e0 = X.edge_off[v], e1 = X.edge_off[v + 1];
       const uint32_t b0 = X.bpf_off[v], b1 = X.bpf_off[v + 1];
@@ -786,6 +805,7 @@ void pack_x(const Example& X, const KeyTables& K, XOut& O) {
       const bool loop = level[v] == 0;
       const bool phi = (fl[v] & 2) != 0;
       uint32_t nch = 0;
+      const size_t rec0 = O.xg_ch.size();
       if (phi) {
         // components: per child c a Phi row (type 2) and its Gamma row
         // (type 4), then Gamma_{code,len} of the row itself (type 3)
@@ -854,9 +874,60 @@ void pack_x(const Example& X, const KeyTables& K, XOut& O) {
       xr.P = Pw[v];
       xr.c = (O.nd_b[nid[v]] >> 16) | ((b1 > b0 ? (uint32_t)X.bpf_code[b0] : 0u) << 16) |
              (phi ? 0x80000000u : 0u);
+      if (K.ss_on) {
+        sk::SsRow W;
+        W.xr = xr;
+        W.node = (uint32_t)nid[v];
+        W.user = W.swept = !phi && !loop;
+        size_t t = rec0;
+        auto table = [&](uint32_t key) {
+          W.rec.push_back(sk::SsRec{-1, key, O.xg_ch[t] & 0xffffu, O.xg_ch[t] >> 16, O.xg_clg[t], O.xg_cpf[t],
+                                    O.xg_cty[t]});
+          ++t;
+        };
+        if (phi) {
+          for (; t < O.xg_ch.size();) table(ss_key++);
+          ss_gra.push_back((uint32_t)O.xgrow.size());
+        } else if (!loop) {
+          for (uint32_t k = e0; k < e1; ++k) {
+            const int c = X.edge_to[k];
+            if (fl[c] & 1) {
+              table((uint32_t)c);
+            } else {
+              W.rec.push_back(sk::SsRec{grow_of[c], 0u, 0u, X.edge_gaps[k], 0u, 1.0f, 0});
+              ++t;
+            }
+          }
+        }
+        grow_of[v] = (int32_t)O.xgrow.size();
+        ss_in.push_back(std::move(W));
+      }
       O.xgrow.push_back(xr);
       O.xg_node.push_back((uint32_t)nid[v]);
       ++nlxg;
+    }
+    if (K.ss_on) {
+      sk::SsOut F;
+      if (sk::shared_sums_schedule(std::move(ss_in), K.ss_thr, SK_KNOB("SK_STORE_ALL") != nullptr, F)) {
+        O.xf_row.swap(F.row);
+        O.xf_node.swap(F.node);
+        O.xf_ch.swap(F.ch);
+        O.xf_clg.swap(F.clg);
+        O.xf_cpf.swap(F.cpf);
+        O.xf_cty.swap(F.cty);
+        for (uint32_t r : ss_gra) O.xf_gra_row.push_back(F.new_index[r]);  // (+ the example's base)
+        O.ss_rows = F.n_shared;
+        O.ss_repl = F.n_replaced;
+        O.max_slots = std::max(O.max_slots, F.nslots);
+      } else {  // over a limit of the layout: this example keeps its plain rows
+        O.xf_row = O.xgrow;
+        O.xf_node = O.xg_node;
+        O.xf_ch = O.xg_ch;
+        O.xf_clg = O.xg_clg;
+        O.xf_cpf = O.xg_cpf;
+        O.xf_cty = O.xg_cty;
+        O.xf_gra_row = O.gra_row;
+      }
     }
     if (K.phi_on) {  // this example's phi keys as a bitset (items take unions)
       const size_t W = (K.phi_raw.size() + 63) / 64;
@@ -955,6 +1026,7 @@ int pack_dataset(sk_dataset* ds, std::string& err, const std::function<void()>* 
                                                               (size_t)std::max(1u, std::thread::hardware_concurrency())}));
   const KeyTables K = key_tables(ds->ex, nthr);
   P.gam_key = K.gam_key;
+  P.shared_sums = K.ss_on;
   if (K.phi_on)
     for (uint64_t k : K.phi_raw) {
       P.phi_al.push_back((uint32_t)k);
@@ -981,7 +1053,7 @@ int pack_dataset(sk_dataset* ds, std::string& err, const std::function<void()>* 
 #define SK_BIG(X) X(nd_a) X(nd_b) X(nd_c) X(nd_w) X(nd_nbp) X(nd_P) X(ed) X(bpf_code) X(bpf_p) X(lvl) \
   X(xr_ch) X(xrow) X(xr_node) X(gr_info) X(gr_pf) X(gr_P) X(xg_ch) X(xg_clg) X(xg_cpf) X(xg_cty)    \
   X(phk_idx) X(gra_gidx) X(gra_row) X(xgrow) X(xg_node) X(pos_prof) X(pos_w) X(pos_chr) X(pos_lru)  \
-  X(ex_phi_bits)
+  X(ex_phi_bits) X(xf_row) X(xf_node) X(xf_ch) X(xf_clg) X(xf_cpf) X(xf_cty) X(xf_gra_row)
 #define SK_OFF(f) std::vector<size_t> off_##f(n + 1, 0);
     SK_BIG(SK_OFF)
 #undef SK_OFF
@@ -1006,6 +1078,13 @@ int pack_dataset(sk_dataset* ds, std::string& err, const std::function<void()>* 
       P.ex_gr_base.push_back((int32_t)off_gr_info[e]);
       P.ex_gra_base.push_back((int32_t)off_gra_gidx[e]);
       P.ex_phk_base.push_back((int32_t)off_phk_idx[e]);
+      if (K.ss_on) {
+        P.ex_xf_base.push_back((int32_t)off_xf_row[e]);
+        P.ex_xfch_base.push_back((int32_t)off_xf_ch[e]);
+        P.ex_nlxf.push_back((int32_t)O.xf_row.size());
+        P.ex_ss_rows.push_back(O.ss_rows);
+        P.ex_ss_repl.push_back(O.ss_repl);
+      }
       app(P.ex_big, O.ex_big); app(P.ex_nslots, O.ex_nslots); app(P.ex_nlxg, O.ex_nlxg);
       app(P.ex_gapless, O.ex_gapless); app(P.ex_nl, O.ex_nl); app(P.ex_nlev, O.ex_nlev);
       app(P.ex_nseqs, O.ex_nseqs); app(P.ex_len, O.ex_len); app(P.ex_has_w, O.ex_has_w);
@@ -1033,6 +1112,7 @@ int pack_dataset(sk_dataset* ds, std::string& err, const std::function<void()>* 
         for (int e = nx.fetch_add(1); e < n; e = nx.fetch_add(1)) {
           XOut& O = xo[e];
           for (uint32_t& r : O.gra_row) r += (uint32_t)off_xgrow[e];  // example-local -> dataset row
+          for (uint32_t& r : O.xf_gra_row) r += (uint32_t)off_xf_row[e];
 #define SK_CPY(f) std::copy(O.f.begin(), O.f.end(), P.f.begin() + off_##f[e]);
           SK_BIG(SK_CPY)
 #undef SK_CPY
@@ -1074,6 +1154,32 @@ int pack_dataset(sk_dataset* ds, std::string& err, const std::function<void()>* 
               "[sk pack] gamma schedule: %ld nodes, %ld rows, %ld unstored, %ld slots; stored %ld, reads: "
               "slab %ld gamma %ld phi %ld, from registers %ld\n",
               s_nodes, s_rows, s_nost, s_slots, s_st, s_slab, s_gam, s_phi, s_reg);
+      if (P.shared_sums) {  // the same counts of the factored schedule (the one the kernel runs)
+        long f_rows = 0, f_ss = 0, f_repl = 0, f_st = 0, f_slab = 0, f_gam = 0, f_phi = 0, f_reg = 0;
+        for (int e = 0; e < n; ++e) {
+          f_rows += P.ex_nlxf[e];
+          f_ss += P.ex_ss_rows[e];
+          f_repl += P.ex_ss_repl[e];
+          uint32_t prev = 0xffffu;
+          size_t k = (size_t)P.ex_xfch_base[e];
+          for (size_t r = (size_t)P.ex_xf_base[e]; r < (size_t)P.ex_xf_base[e] + P.ex_nlxf[e]; ++r) {
+            const int ne = P.xf_row[r].a & 0xff;
+            for (int t = 0; t < ne; ++t, ++k) {
+              const uint32_t c = P.xf_ch[k] & 0xffffu;
+              if (c == prev) ++f_reg;
+              else if (c & 0x8000u) ++f_gam;
+              else if (c & 0x4000u) ++f_phi;
+              else ++f_slab;
+            }
+            prev = P.xf_row[r].b >> 16;
+            f_st += prev < 0x4000u;
+          }
+        }
+        fprintf(stderr,
+                "[sk pack] factored schedule: %ld rows, %ld shared sums for %ld records; stored %ld, reads: "
+                "slab %ld gamma %ld phi %ld, from registers %ld\n",
+                f_rows, f_ss, f_repl, f_st, f_slab, f_gam, f_phi, f_reg);
+      }
     }
   }
   // the x-role arrays are final: the caller may start uploading them while
@@ -1230,22 +1336,36 @@ int sk_dataset_upload(sk_context* ctx, sk_dataset* ds) {
     SK_UPX(xrow, xrow)
     SK_UPX(xr_node, xr_node)
     SK_UPX(xr_ch, xr_ch)
-    SK_UPX(xgrow, xgrow)
-    SK_UPX(xg_node, xg_node)
-    SK_UPX(xg_ch, xg_ch)
-    SK_UPX(xg_clg, xg_clg)
-    SK_UPX(xg_cpf, xg_cpf)
-    SK_UPX(ex_xg_base, ex_xg_base)
-    SK_UPX(ex_nlxg, ex_nlxg)
-    SK_UPX(ex_xgch_base, ex_xgch_base)
+    // the gamma schedule the kernel runs: the factored one where it was built
+    if (P.shared_sums) {
+      SK_UPX(xf_row, xgrow)
+      SK_UPX(xf_node, xg_node)
+      SK_UPX(xf_ch, xg_ch)
+      SK_UPX(xf_clg, xg_clg)
+      SK_UPX(xf_cpf, xg_cpf)
+      SK_UPX(xf_cty, xg_cty)
+      SK_UPX(xf_gra_row, gra_row)
+      SK_UPX(ex_xf_base, ex_xg_base)
+      SK_UPX(ex_nlxf, ex_nlxg)
+      SK_UPX(ex_xfch_base, ex_xgch_base)
+    } else {
+      SK_UPX(xgrow, xgrow)
+      SK_UPX(xg_node, xg_node)
+      SK_UPX(xg_ch, xg_ch)
+      SK_UPX(xg_clg, xg_clg)
+      SK_UPX(xg_cpf, xg_cpf)
+      SK_UPX(xg_cty, xg_cty)
+      SK_UPX(gra_row, gra_row)
+      SK_UPX(ex_xg_base, ex_xg_base)
+      SK_UPX(ex_nlxg, ex_nlxg)
+      SK_UPX(ex_xgch_base, ex_xgch_base)
+    }
     SK_UPX(gr_info, gr_info)
     SK_UPX(gr_pf, gr_pf)
     SK_UPX(gr_P, gr_P)
     SK_UPX(ex_gapless, ex_gapless)
     SK_UPX(gam_key, gam_key)
-    SK_UPX(xg_cty, xg_cty)
     SK_UPX(gra_gidx, gra_gidx)
-    SK_UPX(gra_row, gra_row)
     SK_UPX(phk_idx, phk_idx)
     SK_UPX(phi_al, phi_al)
     SK_UPX(phi_g, phi_g)
@@ -1265,6 +1385,7 @@ int sk_dataset_upload(sk_context* ctx, sk_dataset* ds) {
   const std::function<void()> after_x = [&]() {
     P.xr_ch.insert(P.xr_ch.end(), 8, 0u);  // the kernel prefetches 4 records past a row
     P.xg_ch.insert(P.xg_ch.end(), 8, 0u);
+    if (P.shared_sums) P.xf_ch.insert(P.xf_ch.end(), 8, 0u);
     auto job = [&]() {
       const auto t0 = std::chrono::steady_clock::now();
       xe = up_x();

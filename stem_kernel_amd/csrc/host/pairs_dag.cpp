@@ -479,7 +479,7 @@ int run_dag_pairs(sk_context* ctx, sk_dataset* xs_, sk_dataset* ys_, const sk_ke
     std::fprintf(stderr, "[phi] keys=%zu items=%zu item keys=%zu pairs=%lld phi components=%zu rows=%zu "
                  "classes=%zu sharing=%zu tables=%zu\n",
                  PX.phi_al.size(), plan.items.size(), item_phi.size(), (long long)n, PX.phk_idx.size(),
-                 PX.xgrow.size(), plan.classes.size(), shared, slots);
+                 PX.run_rows().size(), plan.classes.size(), shared, slots);
   }
 
   if (host_stats) th2 = now_ms();
@@ -568,8 +568,8 @@ int run_dag_pairs(sk_context* ctx, sk_dataset* xs_, sk_dataset* ys_, const sk_ke
     }
     const double gap2 = kp->loop_gap * kp->loop_gap;
     const size_t nnd = std::max<size_t>(PX.nd_a.size(), 1);
-    const size_t nxc = std::max<size_t>(PX.xr_ch.size(), 1), nxg = std::max<size_t>(PX.xgrow.size(), 1),
-                 nxgc = std::max<size_t>(PX.xg_ch.size(), 1),
+    const size_t nxc = std::max<size_t>(PX.xr_ch.size(), 1), nxg = std::max<size_t>(PX.run_rows().size(), 1),
+                 nxgc = std::max<size_t>(PX.run_ch().size(), 1),
                  ngh = std::max<size_t>(PX.ex_nl.size() * PX.gam_key.size(), 1),
                  nphk = std::max<size_t>(PX.phk_idx.size(), 1);
     if (!xs_->prep) {

@@ -125,9 +125,30 @@ struct HostPack {
   pvec<uint32_t> gra_gidx, gra_row, phk_idx;
   std::vector<int32_t> ex_gra_base, ex_phk_base;
   pvec<uint64_t> ex_phi_bits;  // per example, the phi keys it uses (bitset)
+  // the factored gamma schedule (host/pack_shared_sums.cpp): the gamma
+  // schedule's rows plus shared-sum combination rows, in arrays of their own
+  // (the xg_* arrays stay the plain schedule); xf_gra_row is gra_row in its
+  // row numbering, ex_ss_rows / ex_ss_repl count each example's shared-sum
+  // rows and the member records they replaced.  Empty unless shared_sums,
+  // which also says that the device image holds them as its gamma schedule.
+  pvec<sk::XRow> xf_row;
+  pvec<uint32_t> xf_node, xf_ch, xf_clg, xf_gra_row;
+  pvec<float> xf_cpf;
+  pvec<uint8_t> xf_cty;
+  std::vector<int32_t> ex_xf_base, ex_nlxf, ex_xfch_base, ex_ss_rows, ex_ss_repl;
+  bool shared_sums = false;
   int32_t max_nl = 0, max_edges = 0, max_bpf = 0, max_nlev = 0, max_len = 0, max_slots = 0;
   int32_t max_nch = 0;
+  // the gamma schedule the kernel runs
+  const pvec<sk::XRow>& run_rows() const { return shared_sums ? xf_row : xgrow; }
+  const pvec<uint32_t>& run_ch() const { return shared_sums ? xf_ch : xg_ch; }
+  const std::vector<int32_t>& run_base() const { return shared_sums ? ex_xf_base : ex_xg_base; }
+  const std::vector<int32_t>& run_nl() const { return shared_sums ? ex_nlxf : ex_nlxg; }
+  const std::vector<int32_t>& run_ch_base() const { return shared_sums ? ex_xfch_base : ex_xgch_base; }
 };
+// the factored schedule's arrays (hashed apart from the lists below)
+#define SK_PACK_F_ARRAYS(X) X(xf_row) X(xf_node) X(xf_ch) X(xf_clg) X(xf_cpf) X(xf_cty) X(xf_gra_row) \
+  X(ex_xf_base) X(ex_nlxf) X(ex_xfch_base) X(ex_ss_rows) X(ex_ss_repl)
 // every packed array: the y-role records (SK_YBIG and their bases) and the
 // x-role / per-example arrays (SK_BIG, the ex_* vectors, the key tables) --
 // sk_dataset_pack_digest and tools/pack_compare.cpp hash them in this order

@@ -605,6 +605,13 @@ class Dataset:
         return dict(zip(("rows", "stored", "slab_reads", "gamma_reads", "phi_reads", "reg_reads",
                          "y_slots"), (a.value for a in v)))
 
+    def shared_sums(self, i: int):
+        """(shared-sum rows, member records they replaced) of example i in the
+        factored gamma schedule (sk_dataset_shared_sums; uploaded datasets)."""
+        v = [C.c_int32() for _ in range(2)]
+        check(lib().sk_dataset_shared_sums(self._h, i, *[C.byref(a) for a in v]))
+        return v[0].value, v[1].value
+
     def dag(self, i: int) -> dict:
         """The DAG of example i (reference numbering), for packer parity."""
         nn, ne, nb, nr, L = self.shape(i)

@@ -74,6 +74,21 @@ def schedule_rows(path, line):
            "source": "host count of the packed x schedule (SK_PACK_STATS=1), 8 B x transfers per example / "
                      "non-leaf x nodes per example"}
     out["bytes_per_cell"]["sum"] = sum(out["bytes_per_cell"].values())
+    # the factored schedule (shared child sums), where the kernel
+    # runs it: the counts above become the plain schedule's, kept beside them
+    f = None
+    for ln in open(path, errors="replace"):
+        f = re.search(r"factored schedule: (\d+) rows, (\d+) shared sums for (\d+) records; stored (\d+), "
+                      r"reads: slab (\d+) gamma (\d+) phi (\d+), from registers (\d+)", ln) or f
+    if f is not None:
+        rows, shared, repl, stored, slab, gam, phi, reg = (int(v) for v in f.groups())
+        per_f = {"stored_rows_written": stored, "slab_rows_read": slab, "gamma_rows_read": gam, "phi_rows_read": phi}
+        plain = {k: out[k] for k in ("x_rows", "rows_from_registers", "row_transfers", "bytes_per_cell")}
+        out.update({"x_rows": rows, "rows_from_registers": reg, "row_transfers": per_f,
+                    "bytes_per_cell": {k: 8.0 * v / n_ex / nl for k, v in per_f.items()},
+                    "shared_sum_rows": shared, "member_records_replaced": repl, "plain_schedule": plain})
+        out["bytes_per_cell"]["sum"] = sum(out["bytes_per_cell"].values())
+        out["transfers_against_plain"] = sum(per_f.values()) / sum(per.values())
     return out
 
 
