@@ -494,6 +494,46 @@ int sk_bpla_gradients(sk_context *ctx, sk_dataset *xs, sk_dataset *ys, const sk_
                       const int32_t *x, const int32_t *y, int64_t n_pairs, double *value,
                       double *grad);
 
+/* Gradients of the protein local-alignment kernel (kind SK_AA_LA), the step
+ * an optimizer of beta, gap and ext takes per pair: for k < n_pairs,
+ * value[k] = BPLAKernel<double,AAMData>::compute_gradients(xs[x[k]], ys[y[k]],
+ * aa_score_table, {1, beta, gap, ext}, d) (bpla_kernel/bpla_kernel.cpp:385-401,
+ * instantiated at :406) over examples whose p_left and p_right are 0 and
+ * p_unpair 1 -- what the noBP kernel scores; the reference's loader leaves the
+ * three vectors empty -- and grad[4k..4k+3] = d = d/d(alpha, beta, gap, ext),
+ * sk_bpla_gradients' layout.  The alpha slot is always +0.0.
+ *
+ * value is NOT sk_pairs' SK_AA_LA value (operator()): compute_gradients'
+ * forward model (BPLA_Forward, :178-243) starts alignments through its states
+ * F_LX = 1, F_LY = j and so weights alignment starts differently.  It is the
+ * model the reference's optimizer differentiates, as sk_bpla_gradients' value
+ * is for RNA; it is not symmetric in (x, y), so ordered pairs matter.
+ *
+ * Uses kp->beta, kp->gap, kp->ext and kp->aa_score_table.  Errors, all before
+ * any launch: SK_ERR_INVALID for a dataset that is not protein or a kind other
+ * than SK_AA_LA (SK_AA_LA_SW has no gradient), SK_ERR_RANGE for an index
+ * outside its dataset, and, on the GPU only, SK_ERR_UNSUPPORTED for a y longer
+ * than sk_la_protein_grad_shape reports for its path (the x length is not
+ * limited).  Host buffers; synchronous.
+ *
+ * The GPU call (csrc/kernels/la_protein_grad.hip) runs pairs of examples with
+ * one residue kind per column on the code kernel and the rest on the profile
+ * kernel; it sums in another order than the reference (about 1e-13 relative)
+ * and gives a pair the same bits whatever the batch around it.  The host call
+ * restates the reference operation by operation and equals it bit for bit;
+ * it needs no upload, and runs pairs on n_threads threads (0: all). */
+int sk_la_protein_gradients(sk_context *ctx, sk_dataset *xs, sk_dataset *ys, const sk_kernel_params *kp,
+                            const int32_t *x, const int32_t *y, int64_t n_pairs, double *value, double *grad);
+int sk_la_protein_gradients_host(sk_dataset *xs, sk_dataset *ys, const sk_kernel_params *kp,
+                                 const int32_t *x, const int32_t *y, int64_t n_pairs, int32_t n_threads,
+                                 double *value, double *grad);
+/* The longest y (columns) of the GPU call's code and profile paths: what a
+ * one-wave workgroup's LDS holds. */
+int sk_la_protein_grad_shape(int32_t *max_y_code, int32_t *max_y_profile);
+/* Kernels the last sk_la_protein_gradients call ran: bit 0 the code kernel,
+ * bit 1 the profile kernel (0 after a refused call). */
+int sk_last_la_protein_grad(const sk_context *ctx, uint32_t *mask);
+
 /* ---------------------------------------------------------------- example files
  * The readers DataLoader<MData>::get (stem_kernel_lite/data.cpp:547-586) pulls
  * examples from, with the reference grammars' exact acceptance (Boost.Spirit

@@ -18,5 +18,8 @@ from .features import (  # noqa: F401
     FeatureSet, PolyKernel, RBFKernel, SigmoidKernel, feature_auc_objective, feature_dots, feature_gram,
     feature_gram_cross, feature_gram_shape, optimize_features,
 )
+from .la_grad import (  # noqa: F401
+    la_auc_objective, la_grad_shape, la_gradient_gram, la_gradients, optimize_la,
+)
 
 __version__ = "0.1.0"

@@ -337,6 +337,7 @@ struct sk_context {
   uint32_t last_stem_classes = 0, last_s4d_classes = 0;
   int32_t last_gamma_shared = 0;  // class launches of the last call that read shared Gamma (and Phi) tables
   uint32_t last_la_protein = 0;   // protein LA kernels of the last call: 1 code, 2 profile
+  uint32_t last_la_protein_grad = 0;  // protein LA gradient kernels of the last gradient call: 1 code, 2 profile
   // RCCL communicator of sk_comm_init (ncclComm_t, csrc/host/shard.cpp)
   void* comm = nullptr;
 };

@@ -506,6 +506,56 @@ __host__ __device__ inline size_t la_prot_prof_lds_bytes(int maxlen, int nwaves)
 hipError_t launch_la_prot_code(const LaProtLaunch& P, int grid, int nwaves, hipStream_t st);
 hipError_t launch_la_prot_prof(const LaProtLaunch& P, int grid, int nwaves, hipStream_t st);
 
+// Protein local-alignment gradients (la_protein_grad.hip;
+// BPLAKernel<double,AAMData>::compute_gradients, bpla_kernel.cpp:385-401, with
+// p_left = p_right = 0, p_unpair = 1 and alpha = 1).
+struct LaProtGradLaunch {
+  LaProtSet xset, yset;
+  const double* table = nullptr;  // 529: [x residue][y residue]
+  double beta = 0.0, gap = 0.0, ext = 0.0;
+  double beta_gap = 0.0, beta_ext = 0.0;  // exp(beta*gap), exp(beta*ext)
+  const int32_t* xs = nullptr;
+  const int32_t* ys = nullptr;
+  const int64_t* oidx = nullptr;  // results of pair k at oidx[k] (nullptr: k)
+  int64_t n_pairs = 0;
+  double* value = nullptr;  // by result index
+  double* grad = nullptr;   // 4 per result index: d/d(alpha, beta, gap, ext)
+  double* scratch = nullptr;
+  int64_t bt_doubles = 0;  // per-wave backward table: 3 states x steps x 64 lanes
+  unsigned long long* pair_counter = nullptr;
+  int32_t lds_max_len = 0;  // even, >= 64 (streamed strips)
+};
+// workgroup LDS of the code gradient kernel: the 24x24 tables of
+// exp(beta * t[a][b]) and t[a][b], then per wave the boundary rows
+// 3 x [maxlen + 2] and the y codes [maxlen]
+__host__ __device__ inline size_t la_prot_grad_code_wave_lds_bytes(int maxlen) {
+  const size_t b = (size_t)3 * (maxlen + 2) * 8 + (size_t)maxlen;
+  return (b + 15) & ~(size_t)15;
+}
+__host__ __device__ inline size_t la_prot_grad_code_lds_bytes(int maxlen, int nwaves) {
+  return (size_t)2 * kAaSlots * kAaSlots * 8 + (size_t)nwaves * la_prot_grad_code_wave_lds_bytes(maxlen);
+}
+// workgroup LDS of the profile gradient kernel: the 23x23 table (padded to
+// 24x24), then per wave the boundary rows 3 x [maxlen + 2] and the y columns
+// [maxlen][24] float (slot 23: the column's sum over the 23 letters)
+__host__ __device__ inline size_t la_prot_grad_prof_wave_lds_bytes(int maxlen) {
+  const size_t b = (size_t)3 * (maxlen + 2) * 8 + (size_t)maxlen * kAaSlots * 4;
+  return (b + 15) & ~(size_t)15;
+}
+__host__ __device__ inline size_t la_prot_grad_prof_lds_bytes(int maxlen, int nwaves) {
+  return (size_t)kAaSlots * kAaSlots * 8 + (size_t)nwaves * la_prot_grad_prof_wave_lds_bytes(maxlen);
+}
+constexpr size_t kLaProtGradLds = 163840;  // a CU's LDS (one workgroup of one wave may take it all)
+// the longest y of each path: the largest even length whose one-wave workgroup fits the LDS
+inline int la_prot_grad_max_y(bool prof) {
+  int len = 64;
+  while ((prof ? la_prot_grad_prof_lds_bytes(len + 2, 1) : la_prot_grad_code_lds_bytes(len + 2, 1)) <= kLaProtGradLds)
+    len += 2;
+  return len;
+}
+hipError_t launch_la_prot_grad_code(const LaProtGradLaunch& P, int grid, int nwaves, hipStream_t st);
+hipError_t launch_la_prot_grad_prof(const LaProtGradLaunch& P, int grid, int nwaves, hipStream_t st);
+
 // Palindrome kernel (simpal.hip; KernelFunc::operator(), simpal/simpal.cpp:236-266).
 constexpr int kSimpalYTile = 1024;   // y entries per LDS tile
 constexpr int kSimpalXBlock = 4;     // x entries per lane (registers)

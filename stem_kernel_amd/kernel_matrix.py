@@ -803,6 +803,41 @@ class Context:
         return svm.auc_objective(K, G, labels, n_folds, C, eps=eps, ctx=self, shrinking=shrinking,
                                  max_iter=svm.DEFAULT_MAX_ITER if max_iter is None else max_iter)
 
+    def la_gradients(self, ds: Dataset, kernel: "LAKernel", x, y, ys: Optional[Dataset] = None):
+        """BPLAKernel<double,AAMData>::compute_gradients for the ordered pairs
+        (ds[x[k]], (ys or ds)[y[k]]) of protein examples on this GPU
+        (sk_la_protein_gradients): returns (values[n], grads[n, 4] =
+        d/d(alpha, beta, gap, ext)), the alpha column +0.0.  values are
+        compute_gradients' return values, the reference's optimizer model, not
+        the values ``gram`` gives for the LAKernel, and K(x, y) != K(y, x):
+        see la_grad.py.  LAKernel(SW=True) raises ValueError."""
+        from . import la_grad
+        return la_grad.la_gradients(ds, kernel, x, y, ys=ys, ctx=self)
+
+    def la_gradient_gram(self, ds: Dataset, kernel: "LAKernel", normalize: bool = False):
+        """The optimizer's Gram and gradient matrices of a protein dataset
+        (CalcMatrix / CalcMatrixN over la_gradients, cells i <= j mirrored):
+        (K[n, n], G[4, n, n]).  K is compute_gradients' value, not ``gram``'s."""
+        from . import la_grad
+        return la_grad.la_gradient_gram(ds, kernel, normalize, ctx=self)
+
+    def la_auc_objective(self, ds: Dataset, kernel: "LAKernel", labels, n_folds: int, C: float,
+                         normalize: bool = False, eps: float = 1e-3, max_iter=None, shrinking: bool = False):
+        """One optimizer step for the protein LA kernel on this GPU:
+        la_gradient_gram, then svm.auc_objective over it.  Returns
+        (f, g, records) with g over (C, beta, gap, ext); the alpha entry is
+        dropped.  The Gram is compute_gradients' value, not ``gram``'s."""
+        from . import la_grad
+        return la_grad.la_auc_objective(ds, kernel, labels, n_folds, C, normalize=normalize, eps=eps,
+                                        max_iter=max_iter, shrinking=shrinking, ctx=self)
+
+    def last_la_protein_grad(self) -> dict:
+        """Kernels the last la_gradients call launched
+        (sk_last_la_protein_grad): ``code`` and ``profile``."""
+        m = C.c_uint32()
+        self._chk(lib().sk_last_la_protein_grad(self._h, C.byref(m)))
+        return dict(code=bool(m.value & 1), profile=bool(m.value & 2))
+
     def feature_auc_objective(self, fs, kernel, n_folds: int, C: float, eps: float = 1e-3, max_iter=None,
                               shrinking: bool = False):
         """One step of the rbf / poly / sigmoid optimizer on this GPU:
