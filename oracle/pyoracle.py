@@ -49,6 +49,15 @@ def oracle():
             getattr(L, n).argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_uint]
         L.orc_si_stem.restype = C.c_double
         L.orc_si_stem.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_uint]
+        L.orc_su_stem_ld.restype = C.c_double
+        L.orc_su_stem_ld.argtypes = L.orc_su_stem.argtypes
+        L.orc_si_stem_ld.restype = C.c_double
+        L.orc_si_stem_ld.argtypes = L.orc_si_stem.argtypes
+        L.orc_su_stem_tab.restype = C.c_double
+        L.orc_su_stem_tab.argtypes = [C.c_void_p, C.c_void_p, _D, C.c_int, C.c_double, C.c_double, C.c_uint]
+        L.orc_si_stem_tab.restype = C.c_double
+        L.orc_si_stem_tab.argtypes = [C.c_void_p, C.c_void_p, _D, C.c_int, C.c_double, C.c_double,
+                                      C.c_double, C.c_uint]
         L.orc_profile_string.restype = C.c_double
         L.orc_profile_string.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_double,
                                          C.c_double, C.c_double]
@@ -372,6 +381,37 @@ def su_stem(x: OMData, y: OMData, loop_gap=0.2, beta=0.3, band=10) -> float:
 
 def si_stem(x: OMData, y: OMData, loop_gap=0.2, stack=1.3, covar=0.8, band=10) -> float:
     return oracle().orc_si_stem(x.h, y.h, loop_gap, stack, covar, band)
+
+
+def su_stem_ld(x: OMData, y: OMData, loop_gap=0.2, beta=0.3, band=10) -> float:
+    """su_stem with the DP's products and sums in long double (same tables),
+    rounded to double once."""
+    return oracle().orc_su_stem_ld(x.h, y.h, loop_gap, beta, band)
+
+
+def si_stem_ld(x: OMData, y: OMData, loop_gap=0.2, stack=1.3, covar=0.8, band=10) -> float:
+    return oracle().orc_si_stem_ld(x.h, y.h, loop_gap, stack, covar, band)
+
+
+def gap_weights(loop_gap: float, n: int) -> np.ndarray:
+    """The oracle's gap-power table: w[0] = 1, w[k] = w[k-1] * loop_gap."""
+    w = np.empty(max(n, 1))
+    w[0] = 1.0
+    for k in range(1, w.size):
+        w[k] = w[k - 1] * loop_gap
+    return w
+
+
+def su_stem_tab(x: OMData, y: OMData, w, gap2: float, beta=0.3, band=10) -> float:
+    """su_stem (double) with the gap-weight table w[k] in place of loop_gap^k
+    and gap2 in place of loop_gap^2 in the node gap score."""
+    w = np.ascontiguousarray(w, dtype=np.float64)
+    return oracle().orc_su_stem_tab(x.h, y.h, w.ctypes.data_as(_D), w.size, gap2, beta, band)
+
+
+def si_stem_tab(x: OMData, y: OMData, w, gap2: float, stack=1.3, covar=0.8, band=10) -> float:
+    w = np.ascontiguousarray(w, dtype=np.float64)
+    return oracle().orc_si_stem_tab(x.h, y.h, w.ctypes.data_as(_D), w.size, gap2, stack, covar, band)
 
 
 def su_str(x: OMData, y: OMData, gap=0.8, alpha=0.2) -> float:

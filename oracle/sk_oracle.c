@@ -695,6 +695,72 @@ double orc_si_stem(const orc_mdata *x, const orc_mdata *y, double loop_gap,
 }
 
 /* ------------------------------------------------------------------ */
+/* Twins of stem_dp for the stem kernels' tests (stem_dp_generic.inc): the
+ * same DP over a caller's gap-weight table in double (_tab), and in long
+ * double rounded to double once (_ld).  stem_dp itself stays as pinned. */
+#define REAL double
+#define SUFFIX(n) n##_d
+#include "stem_dp_generic.inc"
+#undef REAL
+#undef SUFFIX
+#define REAL long double
+#define SUFFIX(n) n##_ld
+#include "stem_dp_generic.inc"
+#undef REAL
+#undef SUFFIX
+
+static void su_params(stem_params *S, double beta, unsigned band) {
+  memset(S, 0, sizeof(*S));
+  S->subst = 1;
+  S->band = band;
+  for (int k = 0; k != 256; ++k) S->co_subst[k] = exp(SK_RIBOSUM_P[k] * beta);
+}
+
+static void si_params(stem_params *S, double stack, double covar, unsigned band) {
+  memset(S, 0, sizeof(*S));
+  S->match = stack;
+  S->mismatch = covar;
+  S->band = band;
+}
+
+static double stem_ld(const stem_params *S, double loop_gap, const orc_mdata *x,
+                      const orc_mdata *y) {
+  int nw = 2 * (x->len > y->len ? x->len : y->len) + 2;
+  double *g = gap_powers(loop_gap, nw); /* the double table stem_dp reads */
+  double r = stem_dp_tab_ld(S, g, nw, loop_gap * loop_gap, x, y);
+  free(g);
+  return r;
+}
+
+double orc_su_stem_ld(const orc_mdata *x, const orc_mdata *y, double loop_gap,
+                      double beta, unsigned band) {
+  stem_params S;
+  su_params(&S, beta, band);
+  return stem_ld(&S, loop_gap, x, y);
+}
+
+double orc_si_stem_ld(const orc_mdata *x, const orc_mdata *y, double loop_gap,
+                      double stack, double covar, unsigned band) {
+  stem_params S;
+  si_params(&S, stack, covar, band);
+  return stem_ld(&S, loop_gap, x, y);
+}
+
+double orc_su_stem_tab(const orc_mdata *x, const orc_mdata *y, const double *w, int nw,
+                       double gap2, double beta, unsigned band) {
+  stem_params S;
+  su_params(&S, beta, band);
+  return stem_dp_tab_d(&S, w, nw, gap2, x, y);
+}
+
+double orc_si_stem_tab(const orc_mdata *x, const orc_mdata *y, const double *w, int nw,
+                       double gap2, double stack, double covar, unsigned band) {
+  stem_params S;
+  si_params(&S, stack, covar, band);
+  return stem_dp_tab_d(&S, w, nw, gap2, x, y);
+}
+
+/* ------------------------------------------------------------------ */
 /* StringKernel<double,MData> (stem_kernel_lite/string_kernel.cpp) */
 static double prof_subst(const double *st, const float *x, const float *y) {
   double v_c = 0.0;

@@ -76,6 +76,21 @@ double orc_su_stem(const orc_mdata *x, const orc_mdata *y, double loop_gap,
  * (def_kernel.h:11-33, score_table.cpp:14-53) */
 double orc_si_stem(const orc_mdata *x, const orc_mdata *y, double loop_gap,
                    double stack, double covar, unsigned band);
+/* Higher-precision twins of the two above (stem_dp_generic.inc): the same
+ * tables (co_subst from the double exp, the double gap powers), the DP's
+ * products and sums in long double, the result rounded to double once. */
+double orc_su_stem_ld(const orc_mdata *x, const orc_mdata *y, double loop_gap,
+                      double beta, unsigned band);
+double orc_si_stem_ld(const orc_mdata *x, const orc_mdata *y, double loop_gap,
+                      double stack, double covar, unsigned band);
+/* The double DP with a caller's gap-weight table w[0..nw) in place of
+ * loop_gap^k and gap2 in place of loop_gap^2 in the node gap score; with
+ * w[k] = w[k-1] * loop_gap (w[0] = 1) and gap2 = loop_gap * loop_gap the
+ * value is orc_su_stem / orc_si_stem bit for bit.  NaN if an edge gap >= nw. */
+double orc_su_stem_tab(const orc_mdata *x, const orc_mdata *y, const double *w, int nw,
+                       double gap2, double beta, unsigned band);
+double orc_si_stem_tab(const orc_mdata *x, const orc_mdata *y, const double *w, int nw,
+                       double gap2, double stack, double covar, unsigned band);
 /* StringKernel<double,MData> (stem_kernel_lite/string_kernel.cpp:10-132):
  * ribosum=1 -> ctor(gap, alpha); ribosum=0 -> ctor(gap, match, mismatch) */
 double orc_profile_string(const orc_mdata *x, const orc_mdata *y, double gap,

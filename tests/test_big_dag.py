@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import stem_kernel_amd as ska
+from tests import stem_long_gaps as slg
 from tests.helpers import rel_err
 
 TOL = 1e-6
@@ -83,6 +84,21 @@ def test_long_gap_edge(gpu_ctx, big_set):
         got = gpu_ctx.pairs(ds, KINDS[kind], [2, 0, 2], [2, 2, 1])
         assert rel_err(got, BIG[f"gap_K{kind}"]) < TOL, kind
         assert 0 in gpu_ctx.last_classes()["stem_maxk"]
+    # At loop_gap 0.2 the edge's weight 0.2^1077 is exactly 0: the case above
+    # proves the route.  At 0.999 and 1.0, band off, the edge reaches every
+    # pair's value (tests/test_stem_visibility_cpu.py); fixture values by the
+    # long-double oracle, tolerance 4 D 2^-53 (tests/stem_long_gaps.py).
+    st = [slg.dag_stats(ds.dag(i)) for i in range(3)]
+    tol = np.array([slg.stem_tol(st[x], st[y]) for x, y in zip([2, 0, 2], [2, 2, 1])])
+    assert tol.max() <= slg.TOL_CAP
+    for g in (0.999, 1.0):
+        for kind, kern in ((0, ska.SuStemKernel(loop_gap=g, len_band=0)), (1, ska.SiStemKernel(loop_gap=g, len_band=0))):
+            got = gpu_ctx.pairs(ds, kern, [2, 0, 2], [2, 2, 1])
+            ref = slg.golden()[f"biggap_g{g}_b0_K{kind}"]
+            err = np.abs(got - ref) / ref
+            print(f"loop_gap {g} kind {kind}: rel err {err}, tolerance {tol}")
+            assert np.all(err <= tol), (g, kind)
+            assert 0 in gpu_ctx.last_classes()["stem_maxk"]
 
 
 @pytest.mark.gpu

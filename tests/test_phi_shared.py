@@ -10,7 +10,11 @@ the x set); with fewer columns than queues, one column, nine unequal columns,
 two register classes in one call and a column shorter than a workgroup's
 waves; and the per-workgroup tables (budget 0) and the single queue must give
 the same bits (experiments build: SK_GAM_TABLE_MB, SK_PHI_TABLE_MB,
-SK_ITEM_QUEUES; run under tests/test_explib.py)."""
+SK_ITEM_QUEUES; run under tests/test_explib.py).
+
+The *_long_gaps tests repeat these at loop_gap 0.98 against the long-double
+oracle at the derived tolerance of tests/stem_long_gaps.py (DESIGN.md §7.1;
+measured on an MI355X: max relative error 1.8e-15, 1.6e-3 of the tolerance)."""
 import functools
 
 import numpy as np
@@ -18,6 +22,7 @@ import pytest
 
 import stem_kernel_amd as ska
 from oracle import pyoracle as po
+from tests import stem_long_gaps as slg
 from tests.helpers import make_examples, mutate_alignment, rel_err
 from tests.test_gamma import _inputs
 from tests.test_gamma_shared import _path_inputs
@@ -25,6 +30,7 @@ from tests.test_gamma_shared import _path_inputs
 pytestmark = pytest.mark.gpu
 
 SEED = 0x9B150
+LONG_GAP = slg.LONG_GAP
 
 
 @functools.lru_cache(maxsize=None)
@@ -38,6 +44,29 @@ def _path_case(band):
     ref = np.array([[po.su_stem(om[i], om[j], 0.4, kern.params.beta, band) for j in range(n)] for i in range(n)])
     ref.setflags(write=False)
     return ds, kern, ref
+
+
+@functools.lru_cache(maxsize=None)
+def _path_case_long(band):
+    """_path_case at loop_gap 0.98 (tests/stem_long_gaps.py): the dataset, the
+    kernel, the long-double oracle's matrix ref[x, y] (whole for band 0, which
+    the queue cases read; x <= y for the others, which only a Gram reads, 1
+    elsewhere) and the per-pair tolerance."""
+    items = _path_inputs(SEED + band)
+    ds, om = make_examples(items)
+    kern = ska.SuStemKernel(loop_gap=LONG_GAP, len_band=band)
+    st = [slg.dag_stats(o.dag()) for o in om]
+    ref = np.array([[po.su_stem_ld(a, b, LONG_GAP, kern.params.beta, band) if band == 0 or j >= i else 1.0
+                     for j, b in enumerate(om)] for i, a in enumerate(om)])
+    tol = slg.tol_matrix(st)
+    assert tol.max() <= slg.TOL_CAP
+    ref.setflags(write=False)
+    tol.setflags(write=False)
+    return ds, kern, ref, tol
+
+
+def _excess(got, ref, tol):
+    return float(np.max(np.abs(got - ref) / (tol * ref)))
 
 
 def _phi_reads(ds):
@@ -116,6 +145,81 @@ def test_item_queues_two_classes(gpu_ctx):
     print(f"classes {classes}, max rel err {err:.3g}")
     assert len(classes) >= 2
     assert err < 1e-6
+
+
+@pytest.mark.parametrize("band", [0, 4])
+def test_shared_phi_tables_oracle_long_gaps(gpu_ctx, band):
+    ds, kern, ref, tol = _path_case_long(band)
+    got = gpu_ctx.gram(ds, kern)
+    shared = gpu_ctx.last_gamma_shared()
+    up = np.triu_indices(len(ds))
+    worst = _excess(got[up], ref[up], tol[up])
+    print(f"band {band}, loop_gap {LONG_GAP}: shared launches {shared}, phi reads {_phi_reads(ds)}, "
+          f"max rel err {rel_err(got[up], ref[up]):.3g}, err / tolerance {worst:.3g}")
+    assert shared > 0
+    assert _phi_reads(ds) > 0
+    assert worst <= 1.0
+
+
+def test_shared_phi_tables_row_and_column_sets_long_gaps(gpu_ctx):
+    train, om = make_examples(_inputs(SEED + 0x10))
+    test, omt = make_examples([ska.random_sequences(1, 70, SEED + 0x11)[0],
+                               mutate_alignment(ska.random_sequences(1, 66, SEED + 0x12)[0], 2, 3, gap=0.0)])
+    kern = ska.SuStemKernel(loop_gap=LONG_GAP)
+    for t in range(2):
+        row = gpu_ctx.test_row(test, t, train, kern)
+        assert gpu_ctx.last_gamma_shared() > 0
+        assert _phi_reads(train) > 0
+        worst, err, tol = slg.su_excess(row, om, [omt[t]], kern)
+        print(f"test {t}, loop_gap {LONG_GAP}: max rel err {err:.3g}, err / tolerance {worst:.3g}")
+        assert tol <= slg.TOL_CAP
+        assert worst <= 1.0
+
+
+@pytest.mark.parametrize("case", sorted(QUEUE_CASES))
+def test_item_queues_oracle_long_gaps(gpu_ctx, case):
+    ds, kern, ref, tol = _path_case_long(0)
+    x, y = _columns(QUEUE_CASES[case], len(ds))
+    got = gpu_ctx.pairs(ds, kern, x, y)
+    worst = _excess(got, ref[x, y], tol[x, y])
+    print(f"{case}, loop_gap {LONG_GAP}: {x.size} pairs, max rel err {rel_err(got, ref[x, y]):.3g}, "
+          f"err / tolerance {worst:.3g}")
+    assert worst <= 1.0
+
+
+def test_item_queues_two_classes_long_gaps(gpu_ctx):
+    items = ska.random_sequences(14, 48, SEED + 0x20) + ska.random_sequences(3, 150, SEED + 0x21)
+    ds, om = make_examples(items)
+    kern = ska.SuStemKernel(loop_gap=LONG_GAP, len_band=0)
+    got = gpu_ctx.gram(ds, kern)
+    classes = gpu_ctx.last_classes()["stem_maxk"]
+    worst, err, tol = slg.su_excess(got, om, om, kern, upper=True)
+    print(f"loop_gap {LONG_GAP}: classes {classes}, max rel err {err:.3g}, err / tolerance {worst:.3g}")
+    assert len(classes) >= 2
+    assert tol <= slg.TOL_CAP
+    assert worst <= 1.0
+
+
+@pytest.mark.explib
+@pytest.mark.parametrize("band", [0, 4])
+def test_table_budgets_and_single_queue_agree_long_gaps(gpu_ctx, band, monkeypatch):
+    """test_per_workgroup_phi_tables_agree and test_single_queue_agrees at
+    loop_gap 0.98, at their bound."""
+    ds, _ = make_examples(_path_inputs(SEED + band))
+    kern = ska.SuStemKernel(loop_gap=LONG_GAP, len_band=band)
+    for k in ("SK_GAM_TABLE_MB", "SK_PHI_TABLE_MB", "SK_ITEM_QUEUES"):
+        monkeypatch.delenv(k, raising=False)
+    on = gpu_ctx.gram(ds, kern)
+    assert gpu_ctx.last_gamma_shared() > 0
+    for knob, value in (("SK_GAM_TABLE_MB", "0"), ("SK_PHI_TABLE_MB", "0"), ("SK_ITEM_QUEUES", "1")):
+        monkeypatch.setenv(knob, value)
+        off = gpu_ctx.gram(ds, kern)
+        if knob != "SK_ITEM_QUEUES":
+            assert gpu_ctx.last_gamma_shared() == 0
+        monkeypatch.delenv(knob)
+        err = rel_err(on, off)
+        print(f"band {band}, loop_gap {LONG_GAP}: default vs {knob}={value}: max rel err {err:.3g}")
+        assert err < 1e-14
 
 
 @pytest.mark.explib

@@ -17,7 +17,12 @@ and 20, the L = 60 set without a length band, and the mixed inputs of
 tests/test_gamma.py, whose gapped alignment makes its y pairs run the full
 schedule (no Gamma tables for that y).  Every test asserts through
 sk_dataset_shared_sums that its x examples have shared-sum rows, and through
-sk_last_classes which register classes ran."""
+sk_last_classes which register classes ran.
+
+The *_long_gaps tests repeat both comparisons at loop_gap 0.98, the first
+against the long-double oracle at the derived tolerance of
+tests/stem_long_gaps.py (measured on an MI355X: max relative
+error 3.3e-15 at L = 200, 7e-4 of the tolerance)."""
 import os
 
 import numpy as np
@@ -25,7 +30,10 @@ import pytest
 
 import stem_kernel_amd as ska
 from oracle import pyoracle as po
+from tests import stem_long_gaps as slg
 from tests.helpers import make_examples, mutate_alignment, rel_err
+
+LONG_GAP = slg.LONG_GAP
 
 pytestmark = pytest.mark.gpu
 
@@ -112,6 +120,42 @@ def test_shared_sums_oracle(gpu_ctx, cases, name):
     print(f"{name}: classes {sorted(ran)}, max rel err {err:.3g}")
     assert classes <= ran, (classes, ran)
     assert err < 1e-6
+
+
+def _long(kern):
+    return ska.SuStemKernel(loop_gap=LONG_GAP, len_band=kern.params.len_band)
+
+
+@pytest.mark.parametrize("name", CASES)
+def test_shared_sums_oracle_long_gaps(gpu_ctx, cases, name):
+    """The same sets at loop_gap 0.98 against the long-double oracle, at the
+    derived tolerance of tests/stem_long_gaps.py."""
+    items, kern, classes, which = cases[name]
+    kern = _long(kern)
+    got, ds, om = _pairs(gpu_ctx, items, kern)
+    ran = set(gpu_ctx.last_classes()["stem_maxk"])
+    _assert_shared(ds, len(items), which)
+    worst, err, tol = slg.su_excess(got, om, om, kern)
+    print(f"{name}, loop_gap {LONG_GAP}: classes {sorted(ran)}, max rel err {err:.3g}, err / tolerance {worst:.3g} "
+          f"(tolerance <= {tol:.3g})")
+    assert classes <= ran, (classes, ran)
+    assert tol <= slg.TOL_CAP
+    assert worst <= 1.0
+
+
+@pytest.mark.explib
+@pytest.mark.parametrize("name", CASES)
+def test_shared_sums_equal_plain_schedule_long_gaps(gpu_ctx, cases, name):
+    items, kern, _, which = cases[name]
+    kern = _long(kern)
+    on, ds_on, _ = _pairs(gpu_ctx, items, kern)
+    off, ds_off, _ = _pairs(gpu_ctx, items, kern, switch=True)
+    n = len(items)
+    _assert_shared(ds_on, n, which)
+    assert all(ds_off.shared_sums(i) == (0, 0) for i in range(n))
+    err = rel_err(on, off)
+    print(f"{name}, loop_gap {LONG_GAP}: factored against plain, max rel err {err:.3g}")
+    assert err < 1e-12
 
 
 @pytest.mark.explib
