@@ -42,7 +42,7 @@
 // one wave per test example, lanes over the training examples, a butterfly
 // sum -- the one place where the order of a sum differs from the host's.
 //
-// Shrinking (SHRINK = true; csrc/host/svm_train.cpp: ShrinkSmo is the same
+// Shrinking (SHRINK = true; csrc/host/svm_train.cpp: its Solver is the same
 // restated on the host).  "Element k" above becomes "position k" of the
 // reference's permuted problem: a thread's registers hold whatever example
 // occupies its positions, with that example's training index (aset) and
@@ -104,7 +104,7 @@
 //     for nu-SVC, alpha for one-class, alpha_k - alpha_{k+l} through LDS for
 //     the SVR types; the decision values from coef as above.
 // coef, rho, obj, r, the iteration count and the counts are the host path's
-// bits (csrc/host/svm_train.cpp: GenSmo).
+// bits (csrc/host/svm_train.cpp: the same Solver).
 //
 // LDS per workgroup: 12 bytes per element slot (48 KiB in the largest class)
 // and the waves' records; the shrink event reuses the slots.  No atomics, no
@@ -1121,6 +1121,42 @@ struct SvmBatch {
   std::vector<int> form;
 };
 
+// The images of a call's checked jobs.  The C-SVC family reads its training
+// list and ypos; the general families get their positions.
+SvmBatch svm_build_batch(const double* targets, int32_t n, const std::vector<SvmJob>& jobs, int64_t sum_train,
+                         int64_t sum_test) {
+  SvmBatch B;
+  B.ypos.assign(n, 0);
+  if (targets)
+    for (int32_t k = 0; k < n; ++k) B.ypos[k] = targets[k] > 0 ? 1 : 0;
+  B.train.resize((size_t)sum_train), B.test.resize((size_t)sum_test);
+  B.prob.resize(jobs.size());
+  B.form.resize(jobs.size());
+  int32_t to = 0, so = 0;
+  for (size_t p = 0; p < jobs.size(); ++p) {
+    const SvmJob& J = jobs[p];
+    SvmProb& D = B.prob[p];
+    D.max_iter = J.max_iter;
+    D.eps = J.eps;
+    D.train_off = to, D.n_train = J.n_train, D.test_off = so, D.n_test = J.n_test;
+    D.svm_type = J.svm_type;
+    if (J.svm_type == SK_SVM_C_SVC) {
+      B.form[p] = kFormCSvc;
+      D.Cp = J.Cp, D.Cn = J.Cn;
+      D.pos_off = 0, D.n_pos = 0;
+    } else {
+      B.form[p] = svm_type_is_nu(J.svm_type) ? kFormNu : kFormGeneral;
+      D.pos_off = (int32_t)B.pos_ty.size();
+      D.n_pos = svm_task_positions(targets, J, B.pos_ty, B.pos_p, B.pos_a0, &D.Cp, &D.Cn);
+    }
+    std::memcpy(B.train.data() + to, J.train, (size_t)J.n_train * 4);
+    if (J.n_test) std::memcpy(B.test.data() + so, J.test, (size_t)J.n_test * 4);
+    to += J.n_train;
+    so += J.n_test;
+  }
+  return B;
+}
+
 constexpr int kSvmForms = 3;
 
 #define SK_SVM_HIP(expr)                                                                          \
@@ -1252,32 +1288,15 @@ extern "C" int sk_svm_train_batch_ex(sk_context* ctx, const double* gram, int32_
     sk::lev_reset(ctx);
     std::string err;
     int64_t sum_train = 0, sum_test = 0;
-    const int rc = sk::svm_check_batch(gram, n, labels, problems, n_problems, alpha_out, dec_out, solutions,
-                                       sk::kSvmMaxTrain, &sum_train, &sum_test, err);
+    const std::vector<sk::SvmJob> jobs = sk::svm_jobs(problems, n_problems);
+    const int rc = sk::svm_check_jobs(sk::kSvmTrainBatch, gram, n, labels, jobs, n_problems, alpha_out, dec_out,
+                                      solutions, true, &sum_train, &sum_test, err);
     if (rc) return sk::ctx_fail(ctx, rc, err);
     if (n_problems == 0) return SK_OK;
     if (sum_train > INT32_MAX || sum_test > INT32_MAX)
       return sk::ctx_fail(ctx, SK_ERR_UNSUPPORTED, "sk_svm_train_batch: over 2^31 list entries in one call");
 
-    sk::SvmBatch B;
-    B.ypos.resize(n);
-    for (int32_t k = 0; k < n; ++k) B.ypos[k] = labels[k] > 0 ? 1 : 0;
-    B.train.resize((size_t)sum_train), B.test.resize((size_t)sum_test);
-    B.prob.resize(n_problems);
-    B.form.assign(n_problems, sk::kFormCSvc);
-    int32_t to = 0, so = 0;
-    for (int p = 0; p < n_problems; ++p) {
-      const sk_svm_problem& P = problems[p];
-      sk::SvmProb& D = B.prob[p];
-      D.max_iter = P.max_iter;
-      D.Cp = P.Cp, D.Cn = P.Cn, D.eps = P.eps;
-      D.train_off = to, D.n_train = P.n_train, D.test_off = so, D.n_test = P.n_test;
-      D.pos_off = 0, D.n_pos = 0, D.svm_type = SK_SVM_C_SVC;
-      std::memcpy(B.train.data() + to, P.train, (size_t)P.n_train * 4);
-      if (P.n_test) std::memcpy(B.test.data() + so, P.test, (size_t)P.n_test * 4);
-      to += P.n_train;
-      so += P.n_test;
-    }
+    const sk::SvmBatch B = sk::svm_build_batch(labels, n, jobs, sum_train, sum_test);
     const int rr = sk::svm_run_batch(ctx, "sk_svm_train_batch", gram, n, B, shrinking != 0, alpha_out, dec_out,
                                      solutions, nullptr, info);
     if (rr) return rr;
@@ -1304,47 +1323,18 @@ extern "C" int sk_svm_solve_batch(sk_context* ctx, const double* gram, int32_t n
     sk::lev_reset(ctx);
     std::string err;
     int64_t sum_train = 0, sum_test = 0;
-    const int rc = sk::svm_check_tasks(gram, n, targets, tasks, n_tasks, coef_out, dec_out, solutions, true,
-                                       &sum_train, &sum_test, err);
+    const std::vector<sk::SvmJob> jobs = sk::svm_jobs(tasks, n_tasks);
+    const int rc = sk::svm_check_jobs(sk::kSvmSolveBatch, gram, n, targets, jobs, n_tasks, coef_out, dec_out,
+                                      solutions, true, &sum_train, &sum_test, err);
     if (rc) return sk::ctx_fail(ctx, rc, err);
     if (n_tasks == 0) return SK_OK;
     if (2 * sum_train > INT32_MAX || sum_test > INT32_MAX)
       return sk::ctx_fail(ctx, SK_ERR_UNSUPPORTED, "sk_svm_solve_batch: over 2^31 list entries in one call");
 
-    sk::SvmBatch B;
-    B.ypos.assign(n, 0);
-    if (targets)
-      for (int32_t k = 0; k < n; ++k) B.ypos[k] = targets[k] > 0 ? 1 : 0;
-    B.train.resize((size_t)sum_train), B.test.resize((size_t)sum_test);
-    B.prob.resize(n_tasks);
-    B.form.resize(n_tasks);
+    // a C-SVC task is sk_svm_train_batch's problem with Cp = Cn = C, and runs its kernel
+    const sk::SvmBatch B = sk::svm_build_batch(targets, n, jobs, sum_train, sum_test);
     bool any_csvc = false;
-    int32_t to = 0, so = 0;
-    for (int p = 0; p < n_tasks; ++p) {
-      const sk_svm_task& T = tasks[p];
-      sk::SvmProb& D = B.prob[p];
-      D.max_iter = T.max_iter;
-      D.eps = T.eps;
-      D.train_off = to, D.n_train = T.n_train, D.test_off = so, D.n_test = T.n_test;
-      D.svm_type = T.svm_type;
-      if (T.svm_type == SK_SVM_C_SVC) {
-        // sk_svm_train_batch's problem with Cp = Cn = C, and its kernel
-        B.form[p] = sk::kFormCSvc;
-        D.Cp = D.Cn = T.C;
-        D.pos_off = 0, D.n_pos = 0;
-        any_csvc = true;
-      } else {
-        B.form[p] = sk::svm_type_is_nu(T.svm_type) ? sk::kFormNu : sk::kFormGeneral;
-        D.pos_off = (int32_t)B.pos_ty.size();
-        double C = 0;
-        D.n_pos = sk::svm_task_positions(targets, T, B.pos_ty, B.pos_p, B.pos_a0, &C);
-        D.Cp = D.Cn = C;
-      }
-      std::memcpy(B.train.data() + to, T.train, (size_t)T.n_train * 4);
-      if (T.n_test) std::memcpy(B.test.data() + so, T.test, (size_t)T.n_test * 4);
-      to += T.n_train;
-      so += T.n_test;
-    }
+    for (int form : B.form) any_csvc |= form == sk::kFormCSvc;
     std::vector<sk_svm_solution> csvc(any_csvc ? n_tasks : 0);
     const int rr = sk::svm_run_batch(ctx, "sk_svm_solve_batch", gram, n, B, false, coef_out, dec_out,
                                      any_csvc ? csvc.data() : nullptr, solutions, nullptr);

@@ -122,6 +122,25 @@ def _problem(p, default_train):
             int(p.get("max_iter", DEFAULT_MAX_ITER)))
 
 
+def _marshal(K, n, labels, ps, struct, fill, solution):
+    """The parsed problems ps (train and test first in each) as a call sees
+    them: (the leading arguments with the array of `struct`, whose other
+    fields fill(a, p) sets; the offsets of each problem's slice of the two
+    outputs; the outputs; the array of `solution` records)."""
+    arr = (struct * max(len(ps), 1))()
+    for a, p in zip(arr, ps):
+        train, test = p[0], p[1]
+        a.train, a.n_train = train.ctypes.data_as(_lib._I32P), len(train)
+        a.test, a.n_test = (test.ctypes.data_as(_lib._I32P) if len(test) else None), len(test)
+        fill(a, p)
+    aoff = np.concatenate([[0], np.cumsum([len(p[0]) for p in ps])]).astype(np.int64)
+    doff = np.concatenate([[0], np.cumsum([len(p[1]) for p in ps])]).astype(np.int64)
+    out = np.zeros(max(int(aoff[-1]), 1))
+    dec = np.zeros(max(int(doff[-1]), 1))
+    args = (K.ctypes.data_as(_lib._F64P), n, labels.ctypes.data_as(_lib._F64P), arr, len(ps))
+    return args, aoff, doff, out, dec, (solution * max(len(ps), 1))()
+
+
 def _solve_tasks(K, n, labels, problems, every, ctx, n_threads):
     """The problems that name an svm_type: sk_svm_solve_batch[_host]."""
     ps = []
@@ -134,17 +153,10 @@ def _solve_tasks(K, n, labels, problems, every, ctx, n_threads):
         c = float(p.get("C", p.get("Cp", 1.0)))
         ps.append((train, test, SVM_TYPES[p["svm_type"]], c, float(p.get("nu", 0.5)), float(p.get("p", 0.1)), eps,
                    mi, p["svm_type"]))
-    arr = (_lib.SvmTask * max(len(ps), 1))()
-    for a, (train, test, ty, c, nu, tube, eps, mi, _) in zip(arr, ps):
-        a.train, a.n_train = train.ctypes.data_as(_lib._I32P), len(train)
-        a.test, a.n_test = (test.ctypes.data_as(_lib._I32P) if len(test) else None), len(test)
-        a.svm_type, a.C, a.nu, a.p, a.eps, a.max_iter = ty, c, nu, tube, eps, mi
-    aoff = np.concatenate([[0], np.cumsum([len(p[0]) for p in ps])]).astype(np.int64)
-    doff = np.concatenate([[0], np.cumsum([len(p[1]) for p in ps])]).astype(np.int64)
-    coef = np.zeros(max(int(aoff[-1]), 1))
-    dec = np.zeros(max(int(doff[-1]), 1))
-    sol = (_lib.SvmTaskSolution * max(len(ps), 1))()
-    args = (K.ctypes.data_as(_lib._F64P), n, labels.ctypes.data_as(_lib._F64P), arr, len(ps))
+    def fill(a, p):
+        a.svm_type, a.C, a.nu, a.p, a.eps, a.max_iter = p[2:8]
+
+    args, aoff, doff, coef, dec, sol = _marshal(K, n, labels, ps, _lib.SvmTask, fill, _lib.SvmTaskSolution)
     outs = (coef.ctypes.data_as(_lib._F64P), dec.ctypes.data_as(_lib._F64P), sol)
     if ctx is None:
         check(lib().sk_svm_solve_batch_host(*args, int(n_threads), *outs))
@@ -201,18 +213,11 @@ def svm_train_batch(K, labels, problems: Sequence[dict], ctx=None, n_threads: in
             return _solve_tasks(K, n, labels, problems, every, ctx, n_threads)
         problems = [{k: v for k, v in p.items() if k not in ("svm_type", "nu", "p")} for p in problems]
     ps = [_problem(p, every) for p in problems]
-    arr = (SvmProblem * max(len(ps), 1))()
-    for a, (train, test, cp, cn, eps, mi) in zip(arr, ps):
-        a.train, a.n_train = train.ctypes.data_as(_lib._I32P), len(train)
-        a.test, a.n_test = (test.ctypes.data_as(_lib._I32P) if len(test) else None), len(test)
-        a.Cp, a.Cn, a.eps, a.max_iter = cp, cn, eps, mi
-    aoff = np.concatenate([[0], np.cumsum([len(p[0]) for p in ps])]).astype(np.int64)
-    doff = np.concatenate([[0], np.cumsum([len(p[1]) for p in ps])]).astype(np.int64)
-    alpha = np.zeros(max(int(aoff[-1]), 1))
-    dec = np.zeros(max(int(doff[-1]), 1))
-    sol = (SvmSolution * max(len(ps), 1))()
-    args = (K.ctypes.data_as(_lib._F64P), n, labels.ctypes.data_as(_lib._F64P), arr, len(ps))
-    info = (_lib.SvmShrinkInfo * max(len(ps), 1))()
+    def fill(a, p):
+        a.Cp, a.Cn, a.eps, a.max_iter = p[2:6]
+
+    args, aoff, doff, alpha, dec, sol = _marshal(K, n, labels, ps, SvmProblem, fill, SvmSolution)
+    info =(_lib.SvmShrinkInfo * max(len(ps), 1))()
     outs = (alpha.ctypes.data_as(_lib._F64P), dec.ctypes.data_as(_lib._F64P), sol, info)
     flag = 1 if shrinking else 0
     if ctx is None:

@@ -5,7 +5,9 @@
 // and runs it; the 2 l positions of the SVR types index every per-position
 // array of the solver, which is where an off-by-l would hide.  Every buffer
 // is allocated at its exact size, so a write past n_train coefficients or
-// n_test decision values is a heap overflow the sanitizer reports.
+// n_test decision values is a heap overflow the sanitizer reports.  It also
+// runs C-SVC through sk_svm_train_batch_host_ex with shrinking off and on
+// (c_svc_with_and_without_shrinking below).
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -20,6 +22,72 @@ uint64_t splitmix64(uint64_t& s) {
   z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
   z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
   return z ^ (z >> 31);
+}
+
+// C-SVC through sk_svm_train_batch_host_ex, shrinking off and on: the same
+// solver, which with shrinking swaps the entries of every per-position array,
+// reads rows over the inactive tail and rebuilds the gradient there.  One
+// integer Gram (K = A A^T / 4, n = 48, d = 3) with a permuted training list and
+// Cp != Cn: a problem that shrinks, runs the unshrink branch and regrows its
+// active set; the same stopped by max_iter between two shrink calls; and a
+// shorter list.  Prints what it saw (the test asserts the counts) and returns
+// the number of failures.
+int c_svc_with_and_without_shrinking() {
+  const int n = 48, d = 3;
+  uint64_t s = 0x5A17E10E;
+  std::vector<int> A((size_t)n * d);
+  for (int& a : A) a = (int)(splitmix64(s) % 7) - 3;
+  std::vector<double> K((size_t)n * n), y(n);
+  for (int r = 0; r < n; ++r)
+    for (int c = 0; c < n; ++c) {
+      long v = 0;
+      for (int k = 0; k < d; ++k) v += (long)A[r * d + k] * A[c * d + k];
+      K[(size_t)r * n + c] = std::ldexp((double)v, -2);
+    }
+  for (int r = 0; r < n; ++r) y[r] = (splitmix64(s) & 1) ? 1.0 : -1.0;
+  y[0] = 1.0, y[1] = -1.0;
+  std::vector<int32_t> train, test;
+  for (int k = 0; k < n; ++k) train.push_back((k * 37 + 5) % n);
+  for (int k = 0; k < n; k += 5) test.push_back(n - 1 - k);
+  const sk_svm_problem problems[3] = {
+      {train.data(), n, test.data(), (int32_t)test.size(), 16.0, 8.0, 1e-3, 1000000},
+      {train.data(), n, test.data(), (int32_t)test.size(), 16.0, 8.0, 1e-3, 100},
+      {train.data(), 30, nullptr, 0, 1.0, 0.25, 1e-3, 1000000},
+  };
+  int failures = 0, capped = 0, shrunk = 0, regrown = 0;
+  for (int shrinking = 0; shrinking < 2; ++shrinking) {
+    std::vector<double> alpha(n + n + 30), dec(2 * test.size());
+    sk_svm_solution sol[3];
+    sk_svm_shrink_info info[3];
+    const int rc = sk_svm_train_batch_host_ex(K.data(), n, y.data(), problems, 3, 2, shrinking, alpha.data(), dec.data(),
+                                              sol, info);
+    if (rc != SK_OK) return failures + 1;
+    const double* a = alpha.data();
+    for (int p = 0; p < 3; ++p) {
+      const sk_svm_problem& P = problems[p];
+      const sk_svm_shrink_info& I = info[p];
+      std::printf("c_svc problem %d shrinking %d: status %d iterations %lld rho %.6g obj %.6g shrink_calls %d "
+                  "shrunk_calls %d min_active %d unshrunk %d regrown %d reconstructions %d resumed %d\n",
+                  p, shrinking, sol[p].status, (long long)sol[p].iterations, sol[p].rho, sol[p].obj, I.shrink_calls,
+                  I.shrunk_calls, I.min_active, I.unshrunk, I.regrown, I.reconstructions, I.resumed);
+      for (int k = 0; k < P.n_train; ++k)
+        if (!(a[k] >= 0 && a[k] <= (y[P.train[k]] > 0 ? P.Cp : P.Cn))) {
+          ++failures;
+          break;
+        }
+      a += P.n_train;
+      if (sol[p].status != (P.max_iter == 100 ? SK_SVM_NOT_CONVERGED : SK_SVM_CONVERGED) || !std::isfinite(sol[p].rho))
+        ++failures;
+      if (!shrinking && (I.shrink_calls || I.shrunk_calls || I.min_active != P.n_train || I.unshrunk || I.regrown ||
+                         I.reconstructions || I.resumed))
+        ++failures;
+      capped += sol[p].status == SK_SVM_NOT_CONVERGED;
+      shrunk += I.shrunk_calls > 0;
+      regrown += I.unshrunk == 1 && I.regrown == 1;
+    }
+  }
+  std::printf("c_svc: capped %d shrunk %d regrown %d\n", capped, shrunk, regrown);
+  return failures;
 }
 
 }  // namespace
@@ -92,6 +160,7 @@ int main() {
   if (sk_svm_solve_batch_host(K.data(), n, target.data(), &bad, 1, 1, coef.data(), dec.data(), sol.data()) !=
       SK_ERR_INVALID)
     ++failures;
+  failures += c_svc_with_and_without_shrinking();
   if (failures) {
     std::printf("FAILED: %d\n", failures);
     return 1;

@@ -7,6 +7,7 @@ qmatrix.cpp compiled in place, run without shrinking); C-SVC through the new
 call against sk_svm_train_batch; batching, decision values, the refusals, the
 model round trip and KKT sanity.  No GPU."""
 import os
+import re
 import subprocess
 
 import numpy as np
@@ -124,6 +125,15 @@ def test_mixed_batch_equals_each_task_alone_in_any_order():
     for p, s in zip(ps, alone):
         if p["svm_type"] in ("nu_svc", "one_class"):
             assert np.array_equal(bits(s.coef), bits(hexes(p["coef"]))), p["name"]
+    # the c_svc task, solved among the other four types, is its problem through the untyped call
+    q = tasks[-1]
+    assert q["svm_type"] == "c_svc"
+    new = got[order.index(n - 1)]
+    old = ska.svm_train_batch(K, both, [dict(train=q["train"], test=q["test"], C=q["C"], max_iter=q["max_iter"])])[0]
+    assert np.array_equal(bits(new.alpha), bits(old.alpha)) and np.array_equal(bits(new.coef), bits(old.coef))
+    assert np.array_equal(bits(new.decision), bits(old.decision))
+    assert (new.rho, new.obj, new.iterations, new.status, new.n_free, new.n_bound, new.r) == \
+        (old.rho, old.obj, old.iterations, old.status, old.n_free, old.n_bound, 0.0)
 
 
 @pytest.mark.parametrize("name", ["nu_svc: rbf l = 40", "one_class: rbf l = 40", "epsilon_svr: rbf l = 40",
@@ -324,3 +334,9 @@ def test_host_code_under_address_and_undefined_sanitizers(tmp_path):
     out = subprocess.run([exe], capture_output=True, text=True)
     assert out.returncode == 0, out.stdout + out.stderr
     assert "ok: 5 types" in out.stdout
+    # the C-SVC part met what it is there for: a stop at max_iter with shrinking off and on, problems
+    # that shrank, and one whose unshrink branch regrew the active set
+    seen = re.search(r"^c_svc: capped (\d+) shrunk (\d+) regrown (\d+)$", out.stdout, re.M)
+    assert seen, out.stdout
+    capped, shrunk, regrown = map(int, seen.groups())
+    assert capped == 2 and shrunk >= 2 and regrown >= 1, out.stdout
