@@ -1036,6 +1036,13 @@ int sk_last_classes(const sk_context *ctx, uint32_t *stem_maxk_mask, uint32_t *s
  * (csrc/kernels/la_protein.hip): bit 0 the code kernel (pairs of examples
  * whose every column holds one residue kind), bit 1 the profile kernel. */
 int sk_last_la_protein(const sk_context *ctx, uint32_t *mask);
+/* Profile string kernels the last compute call launched
+ * (csrc/kernels/profile_string.hip), in the order one-hot fast kernel, dyadic
+ * fast kernel, general kernel (the naive mode runs on the general kernel):
+ * pairs[k] the number of pairs kernel k took, waves[k] the waves per workgroup
+ * of its launch (0: not launched).  All zero after a call without a string
+ * part. */
+int sk_last_string(const sk_context *ctx, int64_t pairs[3], int32_t waves[3]);
 /* The number of DAG stem class launches of the last compute call that read one
  * Gamma table per y example, built by a table kernel ahead of the launch and
  * shared by every workgroup on that y (0 for a null context).  The other

@@ -91,6 +91,15 @@ def oracle():
                                          C.c_double, C.c_double, _D, _D]
         L.orc_naive_string.restype = C.c_double
         L.orc_naive_string.argtypes = [C.c_char_p, C.c_char_p, C.c_double]
+        L.orc_profile_string_ld.restype = C.c_double
+        L.orc_profile_string_ld.argtypes = L.orc_profile_string.argtypes
+        L.orc_naive_string_ld.restype = C.c_double
+        L.orc_naive_string_ld.argtypes = L.orc_naive_string.argtypes
+        L.orc_profile_string_tab.restype = C.c_double
+        L.orc_profile_string_tab.argtypes = [C.c_void_p, C.c_void_p] + [C.c_void_p] * 4 + \
+            [C.c_int, C.c_double, C.c_double, C.c_double]
+        L.orc_naive_string_tab.restype = C.c_double
+        L.orc_naive_string_tab.argtypes = [C.c_char_p, C.c_char_p, C.c_double] + [C.c_void_p] * 4
         _o = L
     return _o
 
@@ -459,6 +468,65 @@ def kernel_value(kind: int, x: OMData, y: OMData, p) -> float:
 
 def naive_string(x: str, y: str, gap=0.8) -> float:
     return oracle().orc_naive_string(x.encode(), y.encode(), gap)
+
+
+def su_str_ld(x: OMData, y: OMData, gap=0.8, alpha=0.2) -> float:
+    """su_str with the DP's products and sums in long double (the same per-cell
+    factors and gap), rounded to double once."""
+    return oracle().orc_profile_string_ld(x.h, y.h, gap, 1, alpha, 0.0, 0.0)
+
+
+def si_str_ld(x: OMData, y: OMData, gap=0.8, match=1.0, mismatch=0.8) -> float:
+    return oracle().orc_profile_string_ld(x.h, y.h, gap, 0, 0.0, match, mismatch)
+
+
+def naive_string_ld(x: str, y: str, gap=0.8) -> float:
+    return oracle().orc_naive_string_ld(x.encode(), y.encode(), gap)
+
+
+def string_tables(gap: float, lx: int, ly: int) -> dict:
+    """The geometric tables of the string DPs' table twins, as long doubles by
+    repeated products: R[j] = G0[0][j], C[i] = G0[i][0], wh[d] / wv[d] the
+    weight of a horizontal / vertical run of d (all gap^k)."""
+    if np.finfo(np.longdouble).nmant < 63:
+        raise RuntimeError("numpy's longdouble is not the C long double of the oracle")
+
+    def geo(n):
+        w = np.empty(n + 1, dtype=np.longdouble)
+        w[0] = 1
+        for k in range(1, n + 1):
+            w[k] = w[k - 1] * np.longdouble(gap)
+        return w
+    return dict(R=geo(ly), C=geo(lx), wh=geo(ly), wv=geo(lx))
+
+
+def _ldp(t, n):
+    t = np.ascontiguousarray(t, dtype=np.longdouble)
+    if t.size < n + 1:
+        raise ValueError(f"table of {t.size} entries, {n + 1} needed")
+    return t
+
+
+def _tabs(tab, lx, ly):
+    keep = [_ldp(tab["R"], ly), _ldp(tab["C"], lx), _ldp(tab["wh"], ly), _ldp(tab["wv"], lx)]
+    return keep, [C.c_void_p(t.ctypes.data) for t in keep]
+
+
+def su_str_tab(x: OMData, y: OMData, tab: dict, alpha=0.2) -> float:
+    """su_str over the caller's tables (string_tables) instead of gap^k."""
+    keep, p = _tabs(tab, oracle().orc_mdata_seq_len(x.h), oracle().orc_mdata_seq_len(y.h))
+    return oracle().orc_profile_string_tab(x.h, y.h, *p, 1, alpha, 0.0, 0.0)
+
+
+def si_str_tab(x: OMData, y: OMData, tab: dict, match=1.0, mismatch=0.8) -> float:
+    keep, p = _tabs(tab, oracle().orc_mdata_seq_len(x.h), oracle().orc_mdata_seq_len(y.h))
+    return oracle().orc_profile_string_tab(x.h, y.h, *p, 0, 0.0, match, mismatch)
+
+
+def naive_string_tab(x: str, y: str, gap: float, tab: dict) -> float:
+    """naive_string over the caller's tables; gap only for the match weight gap^2."""
+    keep, p = _tabs(tab, len(x), len(y))
+    return oracle().orc_naive_string_tab(x.encode(), y.encode(), gap, *p)
 
 
 def bpla(x: OMData, y: OMData, no_bp: bool, sw: bool, gap, ext, alpha, beta, table16) -> float:

@@ -862,6 +862,141 @@ double orc_naive_string(const char *x, const char *y, double gap) {
 }
 
 /* ------------------------------------------------------------------ */
+/* Twins of the two string DPs above for the string kernels' tests
+ * (tests/string_long_gaps.py).  A cell's factor f[i][j] comes in as the double
+ * oracle computes it -- prof_subst with its float n, the float position
+ * weights, the exp table; g * g for a character match of the naive kernel --
+ * and so does the gap; the DP's products and sums are long double.
+ *   _ld:  the recurrences as written above, rounded to double once;
+ *   _tab: the same DP over four caller tables (long double): R[j] for
+ *         G0[0][j] = g^j, C[i] for G0[i][0] = g^i, wh[d] for the weight g^d of
+ *         a horizontal run of d skipped columns (G1[i][j] = sum_{j' <= j}
+ *         v[i][j'] wh[j - j']) and wv[d] for a vertical run of d rows
+ *         (G0[i][j] = sum_{1 <= i' <= i} G1[i'][j] wv[i - i'] + R[j] wv[i]),
+ *         O(Lx Ly (Lx + Ly)).  stem_dp_generic.inc is the stem DP's pair. */
+static long double *profile_factors(const orc_mdata *xx, const orc_mdata *yy, int ribosum,
+                                    double alpha, double match, double mismatch) {
+  double st[16];
+  for (int i = 0; i != 4; ++i)
+    for (int k = 0; k != 4; ++k)
+      st[i * 4 + k] = ribosum ? exp(SK_RIBOSUM_S[i * 4 + k] * alpha)
+                              : (i == k ? match : mismatch);
+  int sx = xx->len, sy = yy->len;
+  int use_weight = xx->weight != NULL && yy->weight != NULL && sx > 0 && sy > 0;
+  long double *f = (long double *)malloc(sizeof(long double) * ((size_t)sx * sy + 1));
+  for (int i = 0; i != sx; ++i)
+    for (int j = 0; j != sy; ++j) {
+      long double v = prof_subst(st, &xx->prof5[i * 5], &yy->prof5[j * 5]);
+      if (use_weight) v = (long double)xx->weight[i] * (long double)yy->weight[j] * v;
+      f[(size_t)i * sy + j] = v;
+    }
+  return f;
+}
+
+static long double *naive_factors(const char *x, const char *y, double gap) {
+  int nx = (int)strlen(x), ny = (int)strlen(y);
+  double g2 = gap * gap;
+  long double *f = (long double *)malloc(sizeof(long double) * ((size_t)nx * ny + 1));
+  for (int i = 0; i != nx; ++i)
+    for (int j = 0; j != ny; ++j) f[(size_t)i * ny + j] = x[i] == y[j] ? g2 : 0.0;
+  return f;
+}
+
+static double string_dp_ld(int sx, int sy, const long double *f, double gap) {
+  const long double g = gap;
+  size_t n = (size_t)sy + 1;
+  long double *rows = (long double *)malloc(sizeof(long double) * n * 4);
+  long double *K0p = rows, *G0p = K0p + n, *K0c = G0p + n, *G0c = K0c + n;
+  K0p[0] = G0p[0] = 1.0L;
+  for (int j = 1; j != sy + 1; ++j) {
+    K0p[j] = 1.0L;
+    G0p[j] = G0p[j - 1] * g;
+  }
+  for (int i = 1; i != sx + 1; ++i) {
+    long double K1 = 0.0L, G1 = 0.0L;
+    K0c[0] = 1.0L;
+    G0c[0] = G0p[0] * g;
+    for (int j = 1; j != sy + 1; ++j) {
+      long double v = G0p[j - 1] * f[(size_t)(i - 1) * sy + (j - 1)];
+      K1 = v + K1;
+      G1 = v + G1 * g;
+      K0c[j] = K1 + K0p[j];
+      G0c[j] = G1 + G0p[j] * g;
+    }
+    long double *t;
+    t = K0p; K0p = K0c; K0c = t;
+    t = G0p; G0p = G0c; G0c = t;
+  }
+  double ret = (double)K0p[sy];
+  free(rows);
+  return ret;
+}
+
+static double string_dp_tab(int sx, int sy, const long double *f, const long double *R,
+                            const long double *Cc, const long double *wh, const long double *wv) {
+  size_t n = (size_t)sy + 1;
+  /* G1 of every row (G0 sums down a column), G0 of the row above, v of this row */
+  long double *G1 = (long double *)calloc((size_t)(sx + 1) * n + 4 * n, sizeof(long double));
+  long double *G0p = G1 + (size_t)(sx + 1) * n, *G0c = G0p + n, *K0 = G0c + n, *v = K0 + n;
+  for (int j = 0; j != sy + 1; ++j) {
+    K0[j] = 1.0L;
+    G0p[j] = R[j];
+  }
+  for (int i = 1; i != sx + 1; ++i) {
+    long double K1 = 0.0L;
+    long double *G1i = G1 + (size_t)i * n;
+    G0c[0] = Cc[i];
+    for (int j = 1; j != sy + 1; ++j) {
+      v[j] = G0p[j - 1] * f[(size_t)(i - 1) * sy + (j - 1)];
+      K1 = v[j] + K1;
+      long double s = 0.0L;
+      for (int q = 1; q != j + 1; ++q) s += v[q] * wh[j - q];
+      G1i[j] = s;
+      K0[j] = K1 + K0[j];
+      s = R[j] * wv[i];
+      for (int p = 1; p != i + 1; ++p) s += G1[(size_t)p * n + j] * wv[i - p];
+      G0c[j] = s;
+    }
+    long double *t = G0p; G0p = G0c; G0c = t;
+  }
+  double ret = (double)K0[sy];
+  free(G1);
+  return ret;
+}
+
+double orc_profile_string_ld(const orc_mdata *xx, const orc_mdata *yy, double gap,
+                             int ribosum, double alpha, double match, double mismatch) {
+  long double *f = profile_factors(xx, yy, ribosum, alpha, match, mismatch);
+  double r = string_dp_ld(xx->len, yy->len, f, gap);
+  free(f);
+  return r;
+}
+
+double orc_naive_string_ld(const char *x, const char *y, double gap) {
+  long double *f = naive_factors(x, y, gap);
+  double r = string_dp_ld((int)strlen(x), (int)strlen(y), f, gap);
+  free(f);
+  return r;
+}
+
+double orc_profile_string_tab(const orc_mdata *xx, const orc_mdata *yy, const long double *R,
+                              const long double *Cc, const long double *wh, const long double *wv,
+                              int ribosum, double alpha, double match, double mismatch) {
+  long double *f = profile_factors(xx, yy, ribosum, alpha, match, mismatch);
+  double r = string_dp_tab(xx->len, yy->len, f, R, Cc, wh, wv);
+  free(f);
+  return r;
+}
+
+double orc_naive_string_tab(const char *x, const char *y, double gap, const long double *R,
+                            const long double *Cc, const long double *wh, const long double *wv) {
+  long double *f = naive_factors(x, y, gap);
+  double r = string_dp_tab((int)strlen(x), (int)strlen(y), f, R, Cc, wh, wv);
+  free(f);
+  return r;
+}
+
+/* ------------------------------------------------------------------ */
 /* BPLA kernel (bpla_kernel/).  Data<ProfileSequence, list<string>>:
  * profile of all rows + fill_weight over the averaged BPMatrix
  * (bpla_kernel/data.cpp:19-45). */

@@ -105,6 +105,21 @@ int orc_char2rna(int c);
 /* Naive gapped string kernel (string_kernel/string_kernel.cpp:14-85) */
 double orc_naive_string(const char *x, const char *y, double gap);
 
+/* Twins of the two string DPs for the string kernels' tests: the same
+ * recurrences on the same per-cell factors and gap, products and sums in long
+ * double, rounded to double once (_ld); and over four caller tables of long
+ * doubles (_tab): R[0..Ly] for G0[0][j], C[0..Lx] for G0[i][0], wh[0..Ly] the
+ * weight of a horizontal run of d skipped columns, wv[0..Lx] of a vertical
+ * run of d rows (all g^k in the recurrences themselves). */
+double orc_profile_string_ld(const orc_mdata *x, const orc_mdata *y, double gap,
+                             int ribosum, double alpha, double match, double mismatch);
+double orc_naive_string_ld(const char *x, const char *y, double gap);
+double orc_profile_string_tab(const orc_mdata *x, const orc_mdata *y, const long double *R,
+                              const long double *C, const long double *wh, const long double *wv,
+                              int ribosum, double alpha, double match, double mismatch);
+double orc_naive_string_tab(const char *x, const char *y, double gap, const long double *R,
+                            const long double *C, const long double *wh, const long double *wv);
+
 /* BPLA kernel (bpla_kernel/bpla_kernel.cpp:159-174): local-alignment
  * partition function (sw=0, :64-115) or Smith-Waterman score (sw=1,
  * :117-157) over profile columns, with the base-pairing score of BPLAScore

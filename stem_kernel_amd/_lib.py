@@ -106,6 +106,7 @@ SIGNATURES = {
     "sk_dataset_aa_profile": (C.c_int, [_P, C.c_int, _F32P, _F32P]),
     "sk_char2aa": (C.c_int, [C.c_int]),
     "sk_last_la_protein": (C.c_int, [_P, C.POINTER(C.c_uint32)]),
+    "sk_last_string": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
     "sk_dataset_add_palindromes": (C.c_int, [_P, C.c_char_p, C.c_char_p, C.POINTER(C.c_double),
                                              C.c_int32, C.c_int32, C.c_int32]),
     "sk_dataset_add_palindromes_folded": (C.c_int, [_P, _P, C.c_int32, C.POINTER(C.c_char_p),

@@ -391,4 +391,13 @@ int sk_last_la_protein(const sk_context* ctx, uint32_t* mask) {
   return SK_OK;
 }
 
+int sk_last_string(const sk_context* ctx, int64_t pairs[3], int32_t waves[3]) {
+  if (!ctx || !pairs || !waves) return SK_ERR_INVALID;
+  for (int k = 0; k < 3; ++k) {
+    pairs[k] = ctx->last_str_pairs[k];
+    waves[k] = ctx->last_str_waves[k];
+  }
+  return SK_OK;
+}
+
 }  // extern "C"

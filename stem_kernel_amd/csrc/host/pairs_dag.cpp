@@ -491,7 +491,9 @@ int run_dag_pairs(sk_context* ctx, sk_dataset* xs_, sk_dataset* ys_, const sk_ke
   size_t need = 0;
   need += splan.soidx.size() * 8 + n_str_pos * (2 * sizeof(sk::StrPos) + sizeof(sk::StrCode)) + 1024;
   need += (item_phi_off.size() + item_phi.size()) * 4 + 512;
-  need += 256 * 8 + 16 * 8 + (size_t)(max_len + 4) * 8 * 2;
+  // (the string fast kernels read gap^lane for every lane of a wave: 64 powers at least)
+  const int n_gp_str = std::max(max_len + 4, 64);
+  need += 256 * 8 + 16 * 8 + (size_t)(max_len + 4) * 8 + (size_t)n_gp_str * 8;
   need += 1024 + 256;
   need += plan.items.size() * sizeof(int4) + nb * (4 + 8) + nb * 8 * 2 + nb * 4 * 2 + 64 + 8 * 256;
   need += plan.slot_y.size() * 4 + 256;
@@ -503,7 +505,7 @@ int run_dag_pairs(sk_context* ctx, sk_dataset* xs_, sk_dataset* ys_, const sk_ke
   double* d_co = A.take<double>(256);
   double* d_gp_loop = A.take<double>(max_len + 4);
   double* d_st = A.take<double>(16);
-  double* d_gp_str = A.take<double>(max_len + 4);
+  double* d_gp_str = A.take<double>(n_gp_str);
   int4* d_items = A.take<int4>(std::max<size_t>(plan.items.size(), 1));
   int32_t* d_ixs = A.take<int32_t>(std::max<size_t>(nb, 1));
   int64_t* d_oidx = A.take<int64_t>(std::max<size_t>(nb, 1));
@@ -532,7 +534,7 @@ int run_dag_pairs(sk_context* ctx, sk_dataset* xs_, sk_dataset* ys_, const sk_ke
     st[k] = subst ? std::exp(SK_RIBOSUM_S[k] * kp->alpha)
                   : ((k >> 2) == (k & 3) ? kp->match : kp->mismatch);
   const std::vector<double> gl = gap_powers(kp->loop_gap, max_len + 4);
-  const std::vector<double> gs = gap_powers(kp->gap, max_len + 4);
+  const std::vector<double> gs = gap_powers(kp->gap, n_gp_str);
   hipStream_t S = ctx->stream;
   SK_HIP(ctx, sk::h2d(ctx, d_co, co.data(), 256 * 8, S));
   SK_HIP(ctx, sk::h2d(ctx, d_st, st.data(), 16 * 8, S));
@@ -800,8 +802,14 @@ int run_dag_pairs(sk_context* ctx, sk_dataset* xs_, sk_dataset* ys_, const sk_ke
       const int fw = std::min(4, per_cu_w);
       const int64_t fg = std::min<int64_t>((int64_t)ctx->n_cu * std::max(1, per_cu_w / fw), (e - b + fw - 1) / fw);
       SK_HIP(ctx, sk::launch_str_fast(F, (int)fg, fw, SS));
+      ctx->last_str_pairs[oh ? 0 : 1] = e - b;
+      ctx->last_str_waves[oh ? 0 : 1] = fw;
     }
-    if (splan.n_sfast < n) SK_HIP(ctx, sk::launch_str(T, (int)g, w, SS));
+    if (splan.n_sfast < n) {
+      SK_HIP(ctx, sk::launch_str(T, (int)g, w, SS));
+      ctx->last_str_pairs[2] = n - splan.n_sfast;
+      ctx->last_str_waves[2] = w;
+    }
     SK_HIP(ctx, hipEventRecord(ctx->ev3, SS));
     if (side) {  // join before the combine
       SK_HIP(ctx, hipEventRecord(ctx->evj, ctx->side));

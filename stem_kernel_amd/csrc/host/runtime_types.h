@@ -337,6 +337,9 @@ struct sk_context {
   uint32_t last_stem_classes = 0, last_s4d_classes = 0;
   int32_t last_gamma_shared = 0;  // class launches of the last call that read shared Gamma (and Phi) tables
   uint32_t last_la_protein = 0;   // protein LA kernels of the last call: 1 code, 2 profile
+  // string kernels of the last call (sk_last_string): one-hot fast, dyadic fast, general
+  int64_t last_str_pairs[3] = {0, 0, 0};
+  int32_t last_str_waves[3] = {0, 0, 0};  // waves per workgroup of each launch
   uint32_t last_la_protein_grad = 0;  // protein LA gradient kernels of the last gradient call: 1 code, 2 profile
   // RCCL communicator of sk_comm_init (ncclComm_t, csrc/host/shard.cpp)
   void* comm = nullptr;

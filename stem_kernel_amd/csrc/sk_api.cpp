@@ -54,6 +54,7 @@ int run_pairs(sk_context* ctx, sk_dataset* xs_, sk_dataset* ys_, const sk_kernel
   ctx->last_stem_classes = ctx->last_s4d_classes = 0;
   ctx->last_gamma_shared = 0;
   ctx->last_la_protein = 0;
+  for (int k = 0; k < 3; ++k) ctx->last_str_pairs[k] = ctx->last_str_waves[k] = 0;
   if (n == 0) return SK_OK;
   const int nx = (int)xs_->ex.size(), ny = (int)ys_->ex.size();
   for (int64_t k = 0; k < n; ++k)

@@ -958,6 +958,16 @@ class Context:
         self._chk(lib().sk_last_la_protein(self._h, C.byref(m)))
         return dict(code=bool(m.value & 1), profile=bool(m.value & 2))
 
+    def last_string(self) -> dict:
+        """Profile string kernels the last compute call launched
+        (sk_last_string): per kernel ``onehot`` (one-hot fast), ``dyadic``
+        (dyadic fast) and ``general`` (naive mode included) the pair (pairs,
+        waves per workgroup of the launch); (0, 0) for a kernel that did not
+        run."""
+        n, w = (C.c_int64 * 3)(), (C.c_int32 * 3)()
+        self._chk(lib().sk_last_string(self._h, n, w))
+        return {k: (int(n[i]), int(w[i])) for i, k in enumerate(("onehot", "dyadic", "general"))}
+
     def last_gamma_shared(self) -> int:
         """sk_last_gamma_shared: the class launches of the last compute call
         that read one Gamma table per y, built by the table kernel (the others
