@@ -21,7 +21,7 @@ HOST_SRC := $(ROOT)stem_kernel_amd/csrc/host/synth.cpp $(ROOT)stem_kernel_amd/cs
 # the host runtime behind the ABI (they share host/runtime.h, host/runtime_types.h)
 API_SRC := $(ROOT)stem_kernel_amd/csrc/sk_api.cpp $(addprefix $(ROOT)stem_kernel_amd/csrc/host/,context.cpp pack.cpp pack_shared_sums.cpp \
            dataset.cpp dataset_io.cpp fold_gpu.cpp pairs_dag.cpp pairs_bpla.cpp pairs_la_protein.cpp \
-           pairs_simpal.cpp pairs_stem4d.cpp la_protein_grad.cpp)
+           pairs_simpal.cpp pairs_stem4d.cpp la_protein_grad.cpp stem_grad.cpp pairs_stem_grad.cpp)
 HIP_SRC := $(ROOT)stem_kernel_amd/csrc/kernels/dag_stem.hip $(ROOT)stem_kernel_amd/csrc/kernels/profile_string.hip \
            $(ROOT)stem_kernel_amd/csrc/kernels/bpla.hip $(ROOT)stem_kernel_amd/csrc/kernels/stem4d.hip \
            $(ROOT)stem_kernel_amd/csrc/kernels/phmm.hip $(ROOT)stem_kernel_amd/csrc/kernels/bpla_grad.hip \
@@ -29,7 +29,8 @@ HIP_SRC := $(ROOT)stem_kernel_amd/csrc/kernels/dag_stem.hip $(ROOT)stem_kernel_a
            $(ROOT)stem_kernel_amd/csrc/kernels/fold_sample.hip $(ROOT)stem_kernel_amd/csrc/kernels/fold_ali.hip \
            $(ROOT)stem_kernel_amd/csrc/kernels/la_protein.hip $(ROOT)stem_kernel_amd/csrc/kernels/simpal.hip \
            $(ROOT)stem_kernel_amd/csrc/kernels/svm_smo.hip $(ROOT)stem_kernel_amd/csrc/kernels/auc_grad.hip \
-           $(ROOT)stem_kernel_amd/csrc/kernels/feature_gram.hip $(ROOT)stem_kernel_amd/csrc/kernels/la_protein_grad.hip
+           $(ROOT)stem_kernel_amd/csrc/kernels/feature_gram.hip $(ROOT)stem_kernel_amd/csrc/kernels/la_protein_grad.hip \
+           $(ROOT)stem_kernel_amd/csrc/kernels/stem_grad.hip
 HDRS := $(wildcard $(ROOT)stem_kernel_amd/csrc/*/*.h) $(ROOT)include/stem_kernel.h $(ROOT)stem_kernel_amd/csrc/ribosum85_60.inc \
         $(ROOT)stem_kernel_amd/csrc/blosum62.inc
 
@@ -72,6 +73,8 @@ $(BUILD)/host/feature_gram.o: CXXFLAGS += -ffp-contract=off
 $(BUILD)/kernels/feature_gram.o: HIPFLAGS += -ffp-contract=off
 # the protein LA gradients' host path restates the reference operation by operation
 $(BUILD)/host/la_protein_grad.o: CXXFLAGS += -ffp-contract=off
+# the stem gradients' host path restates the reference's DP operation by operation
+$(BUILD)/host/stem_grad.o: CXXFLAGS += -ffp-contract=off
 
 $(LIB): $(HOST_OBJ) $(HIP_OBJ)
 	$(LINK) -o $@ $^ $(LINK_LIBS)
@@ -146,6 +149,7 @@ $(BUILD)/exp/host/svm_train.o: CXXFLAGS += -ffp-contract=off
 $(BUILD)/exp/host/auc_gradient.o: CXXFLAGS += -ffp-contract=off
 $(BUILD)/exp/host/feature_gram.o: CXXFLAGS += -ffp-contract=off
 $(BUILD)/exp/host/la_protein_grad.o: CXXFLAGS += -ffp-contract=off
+$(BUILD)/exp/host/stem_grad.o: CXXFLAGS += -ffp-contract=off
 $(EXP_LIB): $(EXP_OBJ) $(HIP_OBJ)
 	$(LINK) -o $@ $^ $(LINK_LIBS)
 .PHONY: exp

@@ -534,6 +534,53 @@ int sk_la_protein_grad_shape(int32_t *max_y_code, int32_t *max_y_profile);
  * bit 1 the profile kernel (0 after a refused call). */
 int sk_last_la_protein_grad(const sk_context *ctx, uint32_t *mask);
 
+/* Gradients of the DAG stem kernels with respect to their own parameters, the
+ * step an optimizer of loop_gap, beta, stack and covar takes per pair.  The
+ * per-pair function is StemKernel<ST,MData>::operator()
+ * (stem_kernel_lite/stem_kernel.cpp:14-95) differentiated in forward mode:
+ * every DP quantity (K0, G0, K1, G1, v_s, e_s) carries its value and one
+ * tangent per parameter, the product rule applied in the DP's own operation
+ * order.  The reference has no such function (stem_kernel/train.cpp calls an
+ * inside_outside that was never written), so the derivative is defined as the
+ * exact derivative of that DP:
+ *   w[k] = w[k-1] * loop_gap        d/dloop_gap = k * w[k-1]  (0 for k = 0)
+ *   gap2 = loop_gap * loop_gap      d/dloop_gap = loop_gap + loop_gap
+ *   Su:  co_subst[c] = exp(P[c] * beta)       d/dbeta = P[c] * co_subst[c]
+ *   Si:  stack where the pair codes are equal, covar otherwise: indicators
+ * len_band, the node weights and the bp frequencies are data.
+ *
+ * For k < n_pairs, value[k] = K(xs[x[k]], ys[y[k]]) and grad[4k..4k+3] =
+ * d/d(loop_gap, beta, stack, covar), sk_bpla_gradients' four-slot layout; the
+ * slots a kind does not read are +0.0 (stack, covar for the Su kinds, beta for
+ * the Si kinds).  Kinds: SK_SU_STEM, SK_SI_STEM; SK_LSU_STEM (V = beta log Ks:
+ * d/dloop_gap = beta Ks'/Ks, d/dbeta = log Ks + beta (dKs/dbeta) / Ks);
+ * SK_SU_STEM_STR, SK_SI_STEM_STR, SK_LSU_STEM_STR, whose value includes the
+ * string term and whose gradient is the stem part's (the string term does not
+ * depend on these parameters).  Gradients with respect to the string
+ * parameters (gap, alpha, match, mismatch) are not computed.  Under the log
+ * kinds a pair with Ks = 0 has the value sk_pairs returns (-inf) and NaN in
+ * the loop_gap and beta slots.
+ *
+ * Errors, all before any launch: SK_ERR_INVALID for any other kind or an
+ * example built with use_bp = 0, SK_ERR_RANGE for an index outside its
+ * dataset and, on the GPU only, SK_ERR_UNSUPPORTED for a pair whose per-wave
+ * scratch does not fit the call's budget (half of the free device memory).
+ * Host buffers; synchronous.
+ *
+ * The GPU call (csrc/kernels/stem_grad.hip) runs one wavefront per pair; it
+ * sums in another order than the DP above and gives a pair the same bits
+ * whatever the batch around it.  The host call restates the DP operation by
+ * operation in double: its value equals the reference's bit for bit; it needs
+ * no upload, and runs pairs on n_threads threads (0: all). */
+int sk_stem_gradients(sk_context *ctx, sk_dataset *xs, sk_dataset *ys, const sk_kernel_params *kp,
+                      const int32_t *x, const int32_t *y, int64_t n_pairs, double *value, double *grad);
+int sk_stem_gradients_host(sk_dataset *xs, sk_dataset *ys, const sk_kernel_params *kp,
+                           const int32_t *x, const int32_t *y, int64_t n_pairs, int32_t n_threads,
+                           double *value, double *grad);
+/* Kernels the last sk_stem_gradients call ran: bit 0 the Su instantiation
+ * (two tangents), bit 1 the Si instantiation (three) (0 after a refused call). */
+int sk_last_stem_grad(const sk_context *ctx, uint32_t *mask);
+
 /* ---------------------------------------------------------------- example files
  * The readers DataLoader<MData>::get (stem_kernel_lite/data.cpp:547-586) pulls
  * examples from, with the reference grammars' exact acceptance (Boost.Spirit

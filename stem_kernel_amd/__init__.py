@@ -21,5 +21,8 @@ from .features import (  # noqa: F401
 from .la_grad import (  # noqa: F401
     la_auc_objective, la_grad_shape, la_gradient_gram, la_gradients, optimize_la,
 )
+from .stem_grad import (  # noqa: F401
+    optimize_stem, stem_auc_objective, stem_gradient_gram, stem_gradients,
+)
 
 __version__ = "0.1.0"

@@ -186,6 +186,10 @@ SIGNATURES = {
                                                C.c_int32, _F64P, _F64P]),
     "sk_la_protein_grad_shape": (C.c_int, [_I32P, _I32P]),
     "sk_last_la_protein_grad": (C.c_int, [_P, C.POINTER(C.c_uint32)]),
+    "sk_stem_gradients": (C.c_int, [_P, _P, _P, C.POINTER(KernelParams), _I32P, _I32P, C.c_int64, _F64P, _F64P]),
+    "sk_stem_gradients_host": (C.c_int, [_P, _P, C.POINTER(KernelParams), _I32P, _I32P, C.c_int64, C.c_int32,
+                                         _F64P, _F64P]),
+    "sk_last_stem_grad": (C.c_int, [_P, C.POINTER(C.c_uint32)]),
     "sk_seqfile_read": (C.c_int, [C.c_char_p, C.c_int32, C.POINTER(_P)]),
     "sk_seqfile_parse": (C.c_int, [C.c_char_p, C.c_size_t, C.c_int32, C.POINTER(_P)]),
     "sk_seqfile_free": (C.c_int, [_P]),

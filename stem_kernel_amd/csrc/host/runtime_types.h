@@ -341,6 +341,7 @@ struct sk_context {
   int64_t last_str_pairs[3] = {0, 0, 0};
   int32_t last_str_waves[3] = {0, 0, 0};  // waves per workgroup of each launch
   uint32_t last_la_protein_grad = 0;  // protein LA gradient kernels of the last gradient call: 1 code, 2 profile
+  uint32_t last_stem_grad = 0;  // stem gradient kernels of the last gradient call: 1 Su, 2 Si
   // RCCL communicator of sk_comm_init (ncclComm_t, csrc/host/shard.cpp)
   void* comm = nullptr;
 };
@@ -468,6 +469,11 @@ int run_stem4d(sk_context* ctx, sk_dataset* xs_, sk_dataset* ys_, const sk_kerne
 // the BPLA gradient driver behind sk_bpla_gradients (host/pairs_bpla.cpp)
 int bpla_gradients(sk_context* ctx, sk_dataset* xs_, sk_dataset* ys_, const sk_kernel_params* kp,
                    const int32_t* x, const int32_t* y, int64_t n, double* value, double* grad);
+// the planner of the stem gradient kernels behind sk_stem_gradients
+// (host/pairs_stem_grad.cpp): the stem part Ks and d/d(loop_gap, beta, stack,
+// covar) of checked pairs, to host buffers (synchronous)
+int stem_gradients_gpu(sk_context* ctx, sk_dataset* xs_, sk_dataset* ys_, const sk_kernel_params* kp,
+                       const int32_t* x, const int32_t* y, int64_t n, double* value, double* grad);
 // example builders of host/dataset.cpp that the GPU folds' adders
 // (host/fold_gpu.cpp), the byte format (host/dataset_io.cpp) and sk_api.cpp
 // use.  kAaMaxRows: protein examples of this many rows or more are refused

@@ -92,6 +92,47 @@ struct StemBigLaunch {
 hipError_t launch_stem_big(const StemBigLaunch& P, int grid, hipStream_t st);
 constexpr int kStemBigWaves = 4;  // waves per workgroup (independent pairs)
 
+// Gradients of the DAG stem kernels (stem_grad.hip): sk_dag_stem_big_kernel's
+// schedule with every per-row vector carried as 1 + NP vectors, the value and
+// one tangent per parameter (NP = 2: loop_gap, beta; NP = 3: loop_gap, stack,
+// covar).  The leaf closed forms and their loop_gap tangents come from the
+// file's own prep kernel (StemGradPrep).
+struct StemGradPrep {
+  DevSet s;
+  const double* gpow = nullptr;   // loop_gap^k
+  const double* dgpow = nullptr;  // k loop_gap^(k-1)
+  double gap2 = 0.0, dgap2 = 0.0;
+  // per non-leaf node of the set: L, SL (level order) and SL in x-row order,
+  // each with its d/dloop_gap
+  double *nd_L = nullptr, *nd_dL = nullptr, *nd_SL = nullptr, *nd_dSL = nullptr;
+  double *xr_SL = nullptr, *xr_dSL = nullptr;
+};
+struct StemGradLaunch {
+  DevSet xset, yset;
+  const double* xr_SL = nullptr;   // of xset (StemGradPrep)
+  const double* xr_dSL = nullptr;
+  const double* co = nullptr;      // 256: node-score table (pair x pair)
+  const double* dco = nullptr;     // 256: its d/dbeta (Su; Si reads the codes)
+  const double* gpow = nullptr;    // loop_gap^k, k < n_gpow
+  const double* dgpow = nullptr;   // k loop_gap^(k-1)
+  int32_t n_gpow = 0;
+  double gap2 = 0.0, dgap2 = 0.0;
+  uint32_t band = 0;
+  const int32_t* xs = nullptr;     // pair k: (x = xs[k], y = ys[k]) -> value[oidx[k]], grad[4 oidx[k]..]
+  const int32_t* ys = nullptr;
+  const int64_t* oidx = nullptr;
+  int64_t n_pairs = 0;
+  double* value = nullptr;
+  double* grad = nullptr;          // 4 per result: d/d(loop_gap, beta, stack, covar)
+  double* scratch = nullptr;       // per wave (1 + NP) x (slots + 3) rows of stride doubles
+  int64_t stride = 0;              // >= max y non-leaf nodes, multiple of 64
+  int64_t wave_doubles = 0;        // (1 + NP) * (slots + 3) * stride
+  int32_t slots = 0;               // G0 rows of the slab
+};
+constexpr int kStemGradWaves = 4;  // waves per workgroup (independent pairs)
+hipError_t launch_stem_grad_prep(const StemGradPrep& P, hipStream_t st);
+hipError_t launch_stem_grad(const StemGradLaunch& P, bool subst, int grid, hipStream_t st);
+
 struct StrLaunch {
   DevSet xset, yset;
   const double* st = nullptr;    // 16: exp(alpha*ribosum_s) or match/mismatch

@@ -831,6 +831,29 @@ class Context:
         return la_grad.la_auc_objective(ds, kernel, labels, n_folds, C, normalize=normalize, eps=eps,
                                         max_iter=max_iter, shrinking=shrinking, ctx=self)
 
+    def stem_gradients(self, ds: Dataset, kernel: _Kernel, x, y, ys: Optional[Dataset] = None):
+        """Value and d/d(loop_gap, beta, stack, covar) of a DAG stem kernel for
+        the ordered pairs (ds[x[k]], (ys or ds)[y[k]]) on this GPU
+        (sk_stem_gradients): (values[n], grads[n, 4]), the slots the kind does
+        not read +0.0.  See stem_grad.py."""
+        from . import stem_grad
+        return stem_grad.stem_gradients(ds, kernel, x, y, ys=ys, ctx=self)
+
+    def stem_gradient_gram(self, ds: Dataset, kernel: _Kernel, normalize: bool = False):
+        """The optimizer's Gram and gradient matrices of a dataset under a DAG
+        stem kernel (cells i <= j mirrored): (K[n, n], G[4, n, n])."""
+        from . import stem_grad
+        return stem_grad.stem_gradient_gram(ds, kernel, normalize, ctx=self)
+
+    def stem_auc_objective(self, ds: Dataset, kernel: _Kernel, labels, n_folds: int, C: float,
+                           normalize: bool = False, eps: float = 1e-3, max_iter=None, shrinking: bool = False):
+        """One optimizer step for a DAG stem kernel on this GPU:
+        stem_gradient_gram, then svm.auc_objective over it.  Returns
+        (f, g, records) with g over (C, the kind's live parameters)."""
+        from . import stem_grad
+        return stem_grad.stem_auc_objective(ds, kernel, labels, n_folds, C, normalize=normalize, eps=eps,
+                                            max_iter=max_iter, shrinking=shrinking, ctx=self)
+
     def last_la_protein_grad(self) -> dict:
         """Kernels the last la_gradients call launched
         (sk_last_la_protein_grad): ``code`` and ``profile``."""

@@ -24,6 +24,7 @@ _SRC_FILES = ("stem_kernel_amd/csrc/sk_api.cpp", "stem_kernel_amd/csrc/host/runt
               "stem_kernel_amd/csrc/host/fold_gpu.cpp", "stem_kernel_amd/csrc/host/pairs_bpla.cpp",
               "stem_kernel_amd/csrc/host/pairs_la_protein.cpp", "stem_kernel_amd/csrc/host/pairs_simpal.cpp",
               "stem_kernel_amd/csrc/host/pairs_stem4d.cpp", "stem_kernel_amd/csrc/host/la_protein_grad.cpp",
+              "stem_kernel_amd/csrc/host/stem_grad.cpp", "stem_kernel_amd/csrc/host/pairs_stem_grad.cpp",
               "stem_kernel_amd/csrc/host/example_build.cpp",
               "stem_kernel_amd/csrc/host/synth.cpp", "stem_kernel_amd/csrc/host/sk_internal.h",
               "stem_kernel_amd/csrc/ribosum85_60.inc")
