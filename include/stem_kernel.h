@@ -264,6 +264,31 @@ int sk_dataset_row_traffic(const sk_dataset *ds, int i, int32_t *rows, int32_t *
  * (packed). */
 int sk_dataset_shared_sums(const sk_dataset *ds, int i, int32_t *shared_rows,
                            int32_t *member_records);
+/* LDS bank model of example i's IY sweep in the y role of the DAG stem kernel
+ * (dag_stem.hip), summed over its sweep chunks as packed: read
+ * cycles (per 32-lane half of a chunk, the largest number of distinct
+ * children on one id mod 32; at least 2 per chunk) and atomic cycles (per
+ * 16-lane group, the largest number of records on one parent id mod 16; at
+ * least 4 per chunk), and the chunks.  The packer deals each chunk's lanes
+ * and numbers equal-length y nodes to lower it.  No counterpart in the
+ * reference.  The dataset must be uploaded (packed). */
+int sk_dataset_sweep_conflicts(const sk_dataset *ds, int i, int32_t *read_cycles,
+                               int32_t *atomic_cycles, int32_t *chunks);
+/* Diagnostic, host only: the y role of example i packed alone (uploaded or
+ * not), in the packer's numbering or, plain != 0, in the plain stable order
+ * by length that the numbering permutes within runs of equal length.  Any
+ * pointer may be NULL; call once for the sizes.  node[n_nodes]: the
+ * level-order non-leaf node each y id holds; len[n_nodes]: its length;
+ * edges[n_edges]: node-major records child:11 | parent:11 | gaps:10;
+ * sweep[64 * n_chunks]: the sweep chunks' lane records (dummies: child ==
+ * parent); first_chunk[max_len + 2]: the first chunk that reads a child of
+ * length >= v; cost[4]: sk_dataset_sweep_conflicts' read and atomic cycles
+ * of this pack, then of the plain order.  A y of the big-y kernel has no
+ * sweep schedule (n_chunks 0, edge records 0). */
+int sk_dataset_y_role(const sk_dataset *ds, int i, int plain, int32_t *n_nodes,
+                      int32_t *n_edges, int32_t *n_chunks, int32_t *max_len, uint32_t *node,
+                      uint32_t *len, uint32_t *edges, uint32_t *sweep, int32_t *first_chunk,
+                      int32_t *cost);
 /* DAG arrays of example i (packer-parity introspection; any pointer may be
  * NULL).  Node arrays have n_nodes entries, edge arrays n_edges (node-major,
  * reference list order), bp arrays n_bpfreq. */

@@ -127,6 +127,9 @@ SIGNATURES = {
     "sk_dataset_shape": (C.c_int, [_P, C.c_int, _I32P, _I32P, _I32P, _I32P, _I32P]),
     "sk_dataset_row_traffic": (C.c_int, [_P, C.c_int, _I32P, _I32P, _I32P, _I32P, _I32P, _I32P, _I32P]),
     "sk_dataset_shared_sums": (C.c_int, [_P, C.c_int, _I32P, _I32P]),
+    "sk_dataset_sweep_conflicts": (C.c_int, [_P, C.c_int, _I32P, _I32P, _I32P]),
+    "sk_dataset_y_role": (C.c_int, [_P, C.c_int, C.c_int, _I32P, _I32P, _I32P, _I32P, _U32P, _U32P, _U32P, _U32P,
+                                    _I32P, _I32P]),
     "sk_dataset_dag": (C.c_int, [_P, C.c_int, _U32P, _U32P, _U32P, _U32P, _F32P, _U32P,
                                  _U32P, _U32P, _U32P, _F32P, _U32P, _F32P]),
     "sk_dataset_profile": (C.c_int, [_P, C.c_int, _F32P, _F32P]),

@@ -99,16 +99,62 @@ static void pack_protein(sk_dataset* ds) {
   }
 }
 
+// LDS bank model of one IY sweep chunk (64 records child:11 | parent:11 |
+// gaps:10 in lane order).  The kernel reads R[child] (ds_read_b64: banks by
+// element mod 32 within each 32-lane half, one cycle per distinct address of
+// the fullest bank) and adds into R[parent] (ds_add_f64: taken as 16-lane
+// groups, element mod 16, one cycle per record of the fullest bank, same
+// address or not).  The lane dealing below and the renumbering pass of pack_y
+// both place records through it, and sk_dataset_sweep_conflicts reports it.
+struct SweepBanks {
+  int at[4][16];            // group -> parent bank -> records
+  uint16_t rd[2][32][32];   // half -> child bank -> its distinct children
+  int rdn[2][32];
+  SweepBanks() { clear(); }
+  void clear() {
+    std::memset(at, 0, sizeof(at));
+    std::memset(rdn, 0, sizeof(rdn));
+  }
+  bool has_child(int h, uint32_t c) const {
+    const int sl = c & 31;
+    for (int t = 0; t < rdn[h][sl]; ++t)
+      if (rd[h][sl][t] == c) return true;
+    return false;
+  }
+  // distinct children on c's bank of half h once c is read there
+  int child_load(int h, uint32_t c) const { return rdn[h][c & 31] + (has_child(h, c) ? 0 : 1); }
+  int parent_load(int g, uint32_t q) const { return at[g][q & 15]; }
+  void put(int g, uint32_t c, uint32_t q) {
+    const int h = g >> 1, sl = c & 31;
+    if (!has_child(h, c)) rd[h][sl][rdn[h][sl]++] = (uint16_t)c;
+    at[g][q & 15]++;
+  }
+  int read_cycles() const {  // per 32-lane half, the fullest bank (floor 2)
+    int s = 0;
+    for (int h = 0; h < 2; ++h) s += *std::max_element(rdn[h], rdn[h] + 32);
+    return s;
+  }
+  int atomic_cycles() const {  // per 16-lane group, the fullest bank (floor 4)
+    int s = 0;
+    for (int g = 0; g < 4; ++g) s += *std::max_element(at[g], at[g] + 16);
+    return s;
+  }
+};
+static void sweep_chunk_cost(const uint32_t lanes[64], int* read_cycles, int* atomic_cycles) {
+  SweepBanks B;
+  for (int l = 0; l < 64; ++l) B.put(l >> 4, lanes[l] & 0x7ff, (lanes[l] >> 11) & 0x7ff);
+  *read_cycles = B.read_cycles();
+  *atomic_cycles = B.atomic_cycles();
+}
+
 // Lane placement of one IY sweep chunk (records child:11 | parent:11 |
-// gaps:10, sorted ids).  The kernel reads R[child] (ds_read_b64: banks by
-// element mod 32 within each 32-lane half) and adds into R[parent]
-// (ds_add_f64: taken as 16-lane groups, element mod 16), so the edges are
-// dealt to the four 16-lane groups greedily to spread both, the parents with
-// most edges in the chunk first; dummies (child == parent, weight 0) take
-// the emptiest slots.
-static void assign_sweep_lanes(const std::vector<int>& take, const std::vector<uint32_t>& er, int nl,
+// gaps:10, sorted ids): the edges are dealt to the four 16-lane groups
+// greedily to spread the child reads and the parent atomics over the banks
+// of SweepBanks, the parents with most edges in the chunk first; dummies
+// (child == parent, weight 0) take the emptiest slots.
+static void assign_sweep_lanes(const int* take, int n, const std::vector<uint32_t>& er, int nl,
                                uint32_t lanes[64]) {
-  const int n = (int)take.size();  // <= 64: fixed arrays, no allocation per chunk
+  // n <= 64: fixed arrays, no allocation per chunk
   // edges per parent in the chunk (a per-thread count table over the 11-bit
   // parent ids, cleared again after use)
   thread_local uint8_t npar[2048];
@@ -126,27 +172,9 @@ static void assign_sweep_lanes(const std::vector<int>& take, const std::vector<u
     for (int i = 0; i < n; ++i) ord[cstart[64 - cntp[i]]++] = i;
   }
   int fill[4] = {0, 0, 0, 0};
-  int at[4][16];         // group -> parent slot load
-  uint32_t rd[2][32][4];  // half -> child slot -> distinct children (up to 4 kept)
-  int rdn[2][32];
-  std::memset(at, 0, sizeof(at));
-  std::memset(rdn, 0, sizeof(rdn));
-  auto child_load = [&](int h, uint32_t c) {
-    const int sl = c & 31;
-    for (int t = 0; t < std::min(rdn[h][sl], 4); ++t)
-      if (rd[h][sl][t] == c) return rdn[h][sl];
-    return rdn[h][sl] + 1;
-  };
+  SweepBanks B;
   auto put = [&](int g, uint32_t r) {
-    const uint32_t c = r & 0x7ff, q = (r >> 11) & 0x7ff;
-    const int h = g >> 1, sl = c & 31;
-    bool seen = false;
-    for (int t = 0; t < std::min(rdn[h][sl], 4); ++t) seen |= rd[h][sl][t] == c;
-    if (!seen) {
-      if (rdn[h][sl] < 4) rd[h][sl][rdn[h][sl]] = c;
-      ++rdn[h][sl];
-    }
-    at[g][q & 15]++;
+    B.put(g, r & 0x7ff, (r >> 11) & 0x7ff);
     lanes[16 * g + fill[g]++] = r;
   };
   for (int oi = 0; oi < n; ++oi) {
@@ -156,7 +184,7 @@ static void assign_sweep_lanes(const std::vector<int>& take, const std::vector<u
     int best = -1, bc = 1 << 30;
     for (int g = 0; g < 4; ++g) {
       if (fill[g] == 16) continue;
-      const int cost = 4 * (child_load(g >> 1, c) + at[g][q & 15] + 1) + fill[g];
+      const int cost = 4 * (B.child_load(g >> 1, c) + B.parent_load(g, q) + 1) + fill[g];
       if (cost < bc) {
         bc = cost;
         best = g;
@@ -169,7 +197,7 @@ static void assign_sweep_lanes(const std::vector<int>& take, const std::vector<u
     while (fill[g] < 16) {
       int bs = 0, bc = 1 << 30;
       for (int sl = 0; sl < 32 && sl < nl1; ++sl) {
-        const int cost = rdn[g >> 1][sl] + at[g][sl & 15];
+        const int cost = B.rdn[g >> 1][sl] + B.at[g][sl & 15];
         if (cost < bc) {
           bc = cost;
           bs = sl;
@@ -179,6 +207,266 @@ static void assign_sweep_lanes(const std::vector<int>& take, const std::vector<u
       put(g, d | (d << 11));
     }
   }
+}
+// one chunk's 64 lane records: dealt (above) or in schedule order, padded
+// with dummy records
+static void sweep_chunk_lanes(const int* take, int n, const std::vector<uint32_t>& er, int nl, bool greedy,
+                              uint32_t lanes[64]) {
+  if (greedy) return assign_sweep_lanes(take, n, er, nl, lanes);
+  for (int j = 0; j < n; ++j) lanes[j] = er[take[j]];
+  for (int j = n; j < 64; ++j) {
+    const uint32_t d = (uint32_t)(j % std::max(nl, 1));
+    lanes[j] = d | (d << 11);
+  }
+}
+
+// The IY sweep schedule of one y as pack_y's list scheduling leaves it:
+// edges (child, parent in ids sorted by length, record er), the chunks'
+// edges in schedule order, and each node's edges as a child.
+struct SweepSchedule {
+  int nl = 0;
+  std::vector<uint32_t> er;
+  std::vector<int> epar, ech;
+  std::vector<int> cb, by_child;        // CSR: a child's edges
+  std::vector<int> chunk_off, chunk_ed;  // CSR: a chunk's edges
+  bool lanes_greedy = true;
+  int nch() const { return (int)chunk_off.size() - 1; }
+};
+struct SweepCost {
+  long read = 0, atomic = 0;
+  long sum() const { return read + atomic; }
+};
+
+// Renumbering of the y nodes within runs of equal length (len[i], by sorted
+// id, non-decreasing).  Nothing but a node's LDS bank depends on its place
+// inside such a run (pack_y), so the ids of a run are permuted to lower the
+// SweepBanks cost summed over the y's chunks, whose composition stays as it
+// is: a greedy pass (nodes by incidence, most first; each takes the free id
+// of its run with the fewest same-bank children and parents already placed
+// in its chunks; ties keep the node's own id, then the lowest), then a
+// bounded number of swaps within runs, proposed from the same counts for
+// the costliest chunk and kept when the dealt chunks' cost falls.  newid is
+// the identity unless the result costs less than the plain order.
+static void renumber_equal_lengths(const SweepSchedule& S, const std::vector<int>& len, std::vector<int>& newid,
+                                   SweepCost& plain, SweepCost& now) {
+  const int nl = S.nl, nch = S.nch(), ne = (int)S.er.size();
+  newid.resize(nl);
+  std::iota(newid.begin(), newid.end(), 0);
+  std::vector<int> cread(nch), catom(nch);
+  auto deal_cost = [&](int ch, const std::vector<uint32_t>& er, int* rd, int* at) {
+    uint32_t lanes[64];
+    sweep_chunk_lanes(S.chunk_ed.data() + S.chunk_off[ch], S.chunk_off[ch + 1] - S.chunk_off[ch], er, nl,
+                      S.lanes_greedy, lanes);
+    sweep_chunk_cost(lanes, rd, at);
+  };
+  plain = SweepCost();
+  for (int ch = 0; ch < nch; ++ch) {
+    deal_cost(ch, S.er, &cread[ch], &catom[ch]);
+    plain.read += cread[ch];
+    plain.atomic += catom[ch];
+  }
+  now = plain;
+  // runs of equal length: r0[i] .. r1[i] holds i
+  std::vector<int> r0(nl), r1(nl);
+  bool any_run = false;
+  for (int i = 0; i < nl;) {
+    int j = i;
+    while (j < nl && len[j] == len[i]) ++j;
+    for (int t = i; t < j; ++t) r0[t] = i, r1[t] = j;
+    any_run |= j - i > 1;
+    i = j;
+  }
+  if (!any_run || nch == 0) return;
+  // a node's chunks: as a child (each chunk once: one address however many
+  // lanes read it) and as a parent (with its records there), CSR by node
+  std::vector<int> coff(nl + 1, 0), poff(nl + 1, 0), cinc, pinc, pmul, pfirst(nl, -1), pcount(nl, 0);
+  {
+    std::vector<uint64_t> ck, pk;  // node:32 | chunk:24 | records:8
+    std::vector<int> lastc(nl, -1), lastp(nl, -1);
+    std::vector<size_t> pat(nl, 0);
+    for (int ch = 0; ch < nch; ++ch)
+      for (int t = S.chunk_off[ch]; t < S.chunk_off[ch + 1]; ++t) {
+        const int f = S.chunk_ed[t], c = S.ech[f], q = S.epar[f];
+        if (lastc[c] != ch) {
+          lastc[c] = ch;
+          ck.push_back(((uint64_t)c << 32) | ((uint64_t)ch << 8));
+        }
+        if (lastp[q] != ch) {
+          lastp[q] = ch;
+          pat[q] = pk.size();
+          pk.push_back(((uint64_t)q << 32) | ((uint64_t)ch << 8));
+        }
+        ++pk[pat[q]];
+      }
+    std::sort(ck.begin(), ck.end());
+    std::sort(pk.begin(), pk.end());
+    for (uint64_t k : ck) {
+      ++coff[(k >> 32) + 1];
+      cinc.push_back((int)((k >> 8) & 0xffffff));
+    }
+    for (uint64_t k : pk) {
+      ++poff[(k >> 32) + 1];
+      pinc.push_back((int)((k >> 8) & 0xffffff));
+      pmul.push_back((int)(k & 0xff));
+    }
+    for (int i = 0; i < nl; ++i) coff[i + 1] += coff[i], poff[i + 1] += poff[i];
+    for (int f = ne - 1; f >= 0; --f) pfirst[S.epar[f]] = f, ++pcount[S.epar[f]];  // a parent's edges are contiguous
+  }
+  // placed same-bank children (distinct) and parent records per chunk
+  std::vector<uint16_t> rc((size_t)nch * 32, 0), ac((size_t)nch * 16, 0);
+  auto score = [&](int v, int id) {
+    int s = 0;
+    for (int t = coff[v]; t < coff[v + 1]; ++t) s += rc[(size_t)cinc[t] * 32 + (id & 31)];
+    for (int t = poff[v]; t < poff[v + 1]; ++t) s += pmul[t] * ac[(size_t)pinc[t] * 16 + (id & 15)];
+    return s;
+  };
+  auto place = [&](int v, int id, int sign) {
+    for (int t = coff[v]; t < coff[v + 1]; ++t) rc[(size_t)cinc[t] * 32 + (id & 31)] += sign;
+    for (int t = poff[v]; t < poff[v + 1]; ++t) ac[(size_t)pinc[t] * 16 + (id & 15)] += sign * pmul[t];
+  };
+  // greedy pass: the nodes alone in their run are where they are; the rest
+  // by incidence (edges as a child and as a parent), most first, then by id
+  std::vector<int> who(nl, -1);  // id -> node
+  {
+    std::vector<int> ord;
+    for (int v = 0; v < nl; ++v) {
+      if (r1[v] - r0[v] == 1) {
+        place(v, v, 1);
+        who[v] = v;
+      } else {
+        ord.push_back(v);
+      }
+    }
+    auto inc = [&](int v) { return S.cb[v + 1] - S.cb[v] + pcount[v]; };
+    std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) { return inc(a) > inc(b); });
+    for (int v : ord) {
+      int sc[32], best = -1;
+      std::fill(sc, sc + 32, -1);
+      for (int j = r0[v]; j < r1[v]; ++j) {
+        if (who[j] >= 0) continue;
+        if (sc[j & 31] < 0) sc[j & 31] = score(v, j);
+        // lower score; then the node's own id; then the lower id (j ascends)
+        if (best < 0 || sc[j & 31] < sc[best & 31] || (sc[j & 31] == sc[best & 31] && j == v)) best = j;
+      }
+      newid[v] = best;
+      who[best] = v;
+      place(v, best, 1);
+    }
+  }
+  // the dealt cost of that numbering
+  std::vector<uint32_t> er(S.er);
+  auto set_id = [&](int v, int id) {
+    for (int t = S.cb[v]; t < S.cb[v + 1]; ++t) er[S.by_child[t]] = (er[S.by_child[t]] & ~0x7ffu) | (uint32_t)id;
+    for (int f = pfirst[v]; f >= 0 && f < pfirst[v] + pcount[v]; ++f)
+      er[f] = (er[f] & ~(0x7ffu << 11)) | ((uint32_t)id << 11);
+  };
+  for (int v = 0; v < nl; ++v)
+    if (newid[v] != v) set_id(v, newid[v]);
+  now = SweepCost();
+  for (int ch = 0; ch < nch; ++ch) {
+    deal_cost(ch, er, &cread[ch], &catom[ch]);
+    now.read += cread[ch];
+    now.atomic += catom[ch];
+  }
+  // swaps within runs, at most kSwapTries proposals
+  {
+    const int kSwapTries = std::min(nch, 32);
+    std::vector<uint8_t> tried(nch, 0);
+    std::vector<int> aff, stamp(nch, -1), asked(nl, -1);
+    for (int it = 0; it < kSwapTries; ++it) {
+      int ch = -1;
+      for (int k = 0; k < nch; ++k)
+        if (!tried[k] && cread[k] + catom[k] > 6 && (ch < 0 || cread[k] + catom[k] > cread[ch] + catom[ch])) ch = k;
+      if (ch < 0) break;
+      // the nodes on the chunk's fullest child and parent banks
+      int mc = 0, mp = 0;
+      for (int b = 0; b < 32; ++b) mc = std::max<int>(mc, rc[(size_t)ch * 32 + b]);
+      for (int b = 0; b < 16; ++b) mp = std::max<int>(mp, ac[(size_t)ch * 16 + b]);
+      int ba = -1, bj = -1, bd = 0;
+      auto propose = [&](int a) {
+        if (r1[a] - r0[a] == 1 || asked[a] == it) return;
+        asked[a] = it;
+        const int ia = newid[a];
+        place(a, ia, -1);
+        const int sa = score(a, ia);
+        for (int j = r0[a]; j < r1[a]; ++j) {
+          if ((j & 31) == (ia & 31)) continue;
+          const int b = who[j];
+          place(b, j, -1);
+          const int d = score(a, j) + score(b, ia) - sa - score(b, j);
+          place(b, j, 1);
+          if (d < bd || (d == bd && d < 0 && (a < ba || (a == ba && j < bj)))) bd = d, ba = a, bj = j;
+        }
+        place(a, ia, 1);
+      };
+      for (int t = S.chunk_off[ch]; t < S.chunk_off[ch + 1]; ++t) {
+        const int f = S.chunk_ed[t], c = S.ech[f], q = S.epar[f];
+        if (mc > 1 && rc[(size_t)ch * 32 + (newid[c] & 31)] == mc) propose(c);
+        if (ac[(size_t)ch * 16 + (newid[q] & 15)] == mp) propose(q);
+      }
+      if (ba < 0) {
+        tried[ch] = 1;
+        continue;
+      }
+      // the chunks either node is in, dealt again with the two ids exchanged
+      const int a = ba, b = who[bj], ia = newid[a], ib = bj;
+      aff.clear();
+      for (int v : {a, b}) {
+        for (int t = coff[v]; t < coff[v + 1]; ++t)
+          if (stamp[cinc[t]] != it) stamp[cinc[t]] = it, aff.push_back(cinc[t]);
+        for (int t = poff[v]; t < poff[v + 1]; ++t)
+          if (stamp[pinc[t]] != it) stamp[pinc[t]] = it, aff.push_back(pinc[t]);
+      }
+      set_id(a, ib);
+      set_id(b, ia);
+      long before = 0, after = 0, dr = 0, da = 0;
+      std::vector<int> nr(aff.size()), na(aff.size());
+      for (size_t k = 0; k < aff.size(); ++k) {
+        deal_cost(aff[k], er, &nr[k], &na[k]);
+        before += cread[aff[k]] + catom[aff[k]];
+        after += nr[k] + na[k];
+        dr += nr[k] - cread[aff[k]];
+        da += na[k] - catom[aff[k]];
+      }
+      if (after < before) {
+        for (size_t k = 0; k < aff.size(); ++k) cread[aff[k]] = nr[k], catom[aff[k]] = na[k];
+        place(a, ia, -1);
+        place(b, ib, -1);
+        place(a, ib, 1);
+        place(b, ia, 1);
+        newid[a] = ib, newid[b] = ia;
+        who[ib] = a, who[ia] = b;
+        now.read += dr;
+        now.atomic += da;
+      } else {
+        set_id(a, ia);
+        set_id(b, ib);
+        tried[ch] = 1;
+      }
+    }
+  }
+  if (now.sum() >= plain.sum()) {  // nothing gained: today's numbering
+    std::iota(newid.begin(), newid.end(), 0);
+    now = plain;
+  }
+}
+
+// The MATCH sums gather R[child] over the node-major edges in rounds of 64
+// from the first edge of a row's length band, so they read children by id
+// too; their rounds' alignment depends on the band and cannot be optimised
+// exactly.  The read model (SweepBanks: distinct children per bank of each
+// 32-lane half) over the 64-edge groups from every start in `starts` to the
+// end of the edges: cycles and groups (SK_PACK_STATS).
+static void match_gather_cost(const std::vector<uint32_t>& child, const std::vector<int>& starts, long* cycles,
+                              long* groups) {
+  const int ne = (int)child.size();
+  for (int s0 : starts)
+    for (int f = s0; f < ne; f += 64) {
+      SweepBanks B;
+      for (int l = 0; l < 64 && f + l < ne; ++l) B.put(l >> 4, child[f + l], 0u);
+      *cycles += B.read_cycles();
+      ++*groups;
+    }
 }
 
 // ---- the phases of pack_dataset
@@ -285,23 +573,44 @@ struct YJob {
   int nb0, ebase, bbase, nl;
   bool big;
 };
-struct YOut {
-  std::vector<uint32_t> ysc, ye2, yn_a, yn_b, yn_c;
-  std::vector<int32_t> ycs;
+// (the records that depend on the order of the nodes, and src: y id -> the
+// example's level-order node)
+struct YRec {
+  std::vector<uint32_t> ysc, ye2, yn_a, yn_b, yn_c, src;
   std::vector<uint4> yrec;
   std::vector<float> yn_w, yn_nbp, yn_p0;
   std::vector<double> yn_P;
+};
+// the records in the plain stable order by length (HostPack's yn_* / ye2 /
+// ysc, as ever) and, where YOpts::renumber, in r the same records with the
+// equal-length nodes renumbered (HostPack's r_*: what the device gets)
+struct YOut : YRec {
+  YRec r;
+  std::vector<int32_t> ycs;
   int nch = 0;
+  // the sweep chunks' SweepBanks cost in the plain order by length and as
+  // packed, and whether the renumbering pass changed the order
+  SweepCost cost_plain, cost;
+  bool renumbered = false;
+  long mg_plain = 0, mg_now = 0, mg_groups = 0;  // match_gather_cost of both orders (YOpts::stats)
   std::string err;
 };
-void pack_y(const HostPack& P, bool sweep_lanes_greedy, const YJob& J, YOut& Y) {
+struct YOpts {
+  bool sweep_lanes_greedy = true;
+  bool renumber = true;  // renumber_equal_lengths (SK_NO_Y_RENUMBER=1: the plain stable order)
+  bool stats = false;    // SK_PACK_STATS: the MATCH gather's read model too
+};
+void pack_y(const HostPack& P, const YOpts& opt, const YJob& J, YOut& Y) {
   const int nl = J.nl, ebase = J.ebase, bbase = J.bbase;
   const bool big = J.big;
   // y-role numbering for the stem kernel: nodes sorted by length (span
   // last - first), so the nodes inside a row's length band are one index
   // range and a node's children (strictly shorter) come before it; edges
   // grouped by parent level (the IY sweep walks levels) and contiguous per
-  // parent, packed child:11 | parent:11 | gaps:10 in sorted ids.
+  // parent, packed child:11 | parent:11 | gaps:10 in sorted ids.  The order
+  // inside a run of equal lengths is free: renumber_equal_lengths chooses it
+  // once the chunks are composed, for a second set of the records (Y.r; the
+  // big-y path keeps the plain order there too).
   {
     std::vector<int> srt(nl);
     std::iota(srt.begin(), srt.end(), 0);
@@ -310,6 +619,7 @@ void pack_y(const HostPack& P, bool sweep_lanes_greedy, const YJob& J, YOut& Y) 
     std::vector<int> pos(nl);
     for (int i = 0; i < nl; ++i) pos[srt[i]] = i;
     const int nb0 = J.nb0;
+    std::vector<int> srt_r, pos_r;  // the renumbered order (Y.r)
     // IY sweep schedule.  The sweep is a stream of chunks of 64 edges: a
     // chunk's R[child] reads are issued after the previous chunk's
     // atomics, so an edge may go into any chunk after the one holding the
@@ -322,8 +632,11 @@ void pack_y(const HostPack& P, bool sweep_lanes_greedy, const YJob& J, YOut& Y) 
       for (int v = 0; v <= lmax + 1; ++v) Y.ycs.push_back(0);
       Y.nch = 0;
     } else {
-      std::vector<uint32_t> er;       // records child:11 | parent:11 | gaps:10
-      std::vector<int> epar, ech;
+      SweepSchedule S;
+      S.nl = nl;
+      S.lanes_greedy = opt.sweep_lanes_greedy;
+      std::vector<uint32_t>& er = S.er;  // records child:11 | parent:11 | gaps:10
+      std::vector<int>&epar = S.epar, &ech = S.ech;
       for (int k = 0; k < nl; ++k) {
         const uint32_t a = P.nd_a[nb0 + k];
         const uint32_t ne = (a >> 16) & 0xff, el = a & 0xffff;
@@ -337,7 +650,9 @@ void pack_y(const HostPack& P, bool sweep_lanes_greedy, const YJob& J, YOut& Y) 
       }
       const int ne_all = (int)er.size();
       // a child's edges in edge order (CSR: one allocation, not one per node)
-      std::vector<int> cb(nl + 1, 0), by_child(ne_all);
+      std::vector<int>&cb = S.cb, &by_child = S.by_child;
+      cb.assign(nl + 1, 0);
+      by_child.resize(ne_all);
       for (int f = 0; f < ne_all; ++f) cb[ech[f] + 1]++;
       for (int i = 0; i < nl; ++i) cb[i + 1] += cb[i];
       {
@@ -366,6 +681,7 @@ void pack_y(const HostPack& P, bool sweep_lanes_greedy, const YJob& J, YOut& Y) 
       // done: parents completed by the chunk just formed; their edges are
       // ready from the next chunk on
       std::vector<int> take, done;
+      S.chunk_off.push_back(0);
       while (!ready.empty()) {
         take.clear();
         done.clear();
@@ -377,17 +693,8 @@ void pack_y(const HostPack& P, bool sweep_lanes_greedy, const YJob& J, YOut& Y) 
           run = std::max<int32_t>(run, (int32_t)(P.nd_b[nb0 + srt[ech[f]]] & 0xffff));
           if (--rem[epar[f]] == 0) done.push_back(epar[f]);
         }
-        if (sweep_lanes_greedy) {
-          uint32_t lanes[64];
-          assign_sweep_lanes(take, er, nl, lanes);
-          Y.ysc.insert(Y.ysc.end(), lanes, lanes + 64);
-        } else {
-          for (int f : take) Y.ysc.push_back(er[f]);
-          for (int j = (int)take.size(); j < 64; ++j) {
-            const uint32_t d = (uint32_t)(j % std::max(nl, 1));
-            Y.ysc.push_back(d | (d << 11));
-          }
-        }
+        S.chunk_ed.insert(S.chunk_ed.end(), take.begin(), take.end());
+        S.chunk_off.push_back((int)S.chunk_ed.size());
         placed += (int)take.size();
         cm.push_back(run);
         for (int q : done) push_edges_of(q);  // ready from the next chunk on
@@ -397,6 +704,41 @@ void pack_y(const HostPack& P, bool sweep_lanes_greedy, const YJob& J, YOut& Y) 
         return;
       }
       const int nch = (int)cm.size();
+      // the chunks are composed: their records dealt to the lanes in the
+      // plain order, then in the order renumber_equal_lengths chooses inside
+      // the runs of equal length
+      auto emit_lanes = [&](const std::vector<uint32_t>& recs, YRec& A) {
+        SweepCost dealt;
+        for (int c = 0; c < nch; ++c) {
+          uint32_t lanes[64];
+          int rd, at;
+          sweep_chunk_lanes(S.chunk_ed.data() + S.chunk_off[c], S.chunk_off[c + 1] - S.chunk_off[c], recs, nl,
+                            opt.sweep_lanes_greedy, lanes);
+          sweep_chunk_cost(lanes, &rd, &at);
+          dealt.read += rd;
+          dealt.atomic += at;
+          A.ysc.insert(A.ysc.end(), lanes, lanes + 64);
+        }
+        return dealt;
+      };
+      Y.cost_plain = Y.cost = emit_lanes(er, Y);
+      if (opt.renumber) {
+        std::vector<int> len(nl), newid;
+        for (int i = 0; i < nl; ++i) len[i] = (int)(P.nd_b[nb0 + srt[i]] & 0xffff);
+        renumber_equal_lengths(S, len, newid, Y.cost_plain, Y.cost);
+        for (int i = 0; i < nl && !Y.renumbered; ++i) Y.renumbered = newid[i] != i;
+        if (Y.renumbered) {
+          srt_r.resize(nl);
+          pos_r.resize(nl);
+          for (int i = 0; i < nl; ++i) srt_r[newid[i]] = srt[i];
+          for (int i = 0; i < nl; ++i) pos_r[srt_r[i]] = i;
+          for (uint32_t& r : er)
+            r = (r & ~0x3fffffu) | (uint32_t)newid[r & 0x7ff] | ((uint32_t)newid[(r >> 11) & 0x7ff] << 11);
+          emit_lanes(er, Y.r);
+        } else {
+          Y.r.ysc = Y.ysc;
+        }
+      }
       // first chunk whose prefix maximum reaches v, v = 0 .. lmax+1
       const int lmax = nl ? (int)(P.nd_b[nb0 + srt[nl - 1]] & 0xffff) : 0;
       for (int v = 0, c = 0; v <= lmax + 1; ++v) {
@@ -408,9 +750,11 @@ void pack_y(const HostPack& P, bool sweep_lanes_greedy, const YJob& J, YOut& Y) 
     // node-major copy of the edges in sorted order (the MATCH sums of a
     // run of consecutive nodes read one contiguous edge range); a node's
     // record keeps its first edge there, E(q) = prefix sum of n_edges
+    auto emit_nodes = [&](const std::vector<int>& srt, const std::vector<int>& pos, YRec& Y) {
     const int ye2_base = (int)Y.ye2.size();
     for (int i = 0; i < nl; ++i) {
       const int k = srt[i];
+      Y.src.push_back((uint32_t)k);
       const uint32_t a = P.nd_a[nb0 + k];
       const uint32_t ne = (a >> 16) & 0xff, el = a & 0xffff;
       const uint32_t nbf = a >> 24, bl = P.nd_b[nb0 + k] >> 16;
@@ -438,6 +782,20 @@ void pack_y(const HostPack& P, bool sweep_lanes_greedy, const YJob& J, YOut& Y) 
       Y.yn_w.push_back(P.nd_w[nb0 + k]);
       Y.yn_nbp.push_back(P.nd_nbp[nb0 + k]);
       Y.yn_P.push_back(P.nd_P[nb0 + k]);
+    }
+    };
+    emit_nodes(srt, pos, Y);
+    if (opt.renumber) emit_nodes(Y.renumbered ? srt_r : srt, Y.renumbered ? pos_r : pos, Y.r);
+    if (opt.stats && opt.renumber && !big) {  // the MATCH gather's reads in both orders, from every length's first edge
+      std::vector<int> starts;
+      std::vector<uint32_t> now, plain;
+      for (int i = 0; i < nl; ++i)
+        if (i == 0 || (Y.yn_b[i] & 0xffff) != (Y.yn_b[i - 1] & 0xffff)) starts.push_back((int)(Y.yn_a[i] & 0xffff));
+      for (uint32_t e : Y.r.ye2) now.push_back(e & 0x7ff);
+      for (uint32_t e : Y.ye2) plain.push_back(e & 0x7ff);
+      long g2 = 0;
+      match_gather_cost(now, starts, &Y.mg_now, &Y.mg_groups);
+      match_gather_cost(plain, starts, &Y.mg_plain, &g2);
     }
   }
 }
@@ -1191,9 +1549,16 @@ int pack_dataset(sk_dataset* ds, std::string& err, const std::function<void()>* 
     const int nthr = (int)std::max<size_t>(1, std::min<size_t>({yjobs.size() / 8 + 1, pcap,
                                                                 (size_t)std::max(1u, std::thread::hardware_concurrency())}));
     std::atomic<size_t> next{0};
+    YOpts yopt;
+    yopt.sweep_lanes_greedy = sweep_lanes_greedy;
+    // SK_NO_Y_RENUMBER=1: the y nodes in the plain stable order by length (A/B)
+    yopt.renumber = !SK_KNOB("SK_NO_Y_RENUMBER");
+    yopt.stats = std::getenv("SK_PACK_STATS") != nullptr;
+    SweepCost yc_plain, yc_now;
+    long y_renum = 0, mg_plain = 0, mg_now = 0, mg_groups = 0;
     auto work = [&]() {
       for (size_t e = next.fetch_add(1); e < yjobs.size(); e = next.fetch_add(1))
-        pack_y(P, sweep_lanes_greedy, yjobs[e], yo[e]);
+        pack_y(P, yopt, yjobs[e], yo[e]);
     };
     run_pool(nthr, work);
     const double ty1 = tnow();
@@ -1216,10 +1581,22 @@ int pack_dataset(sk_dataset* ds, std::string& err, const std::function<void()>* 
       P.ex_ycs_base.push_back((int32_t)off_ycs[e]);
       P.ex_nch.push_back(Y.nch);
       P.max_nch = std::max(P.max_nch, Y.nch);
+      yc_plain.read += Y.cost_plain.read, yc_plain.atomic += Y.cost_plain.atomic;
+      yc_now.read += Y.cost.read, yc_now.atomic += Y.cost.atomic;
+      y_renum += Y.renumbered;
+      mg_plain += Y.mg_plain, mg_now += Y.mg_now, mg_groups += Y.mg_groups;
     }
 #define SK_SIZE(f) P.f.resize(off_##f[ny]);
     SK_YBIG(SK_SIZE)
 #undef SK_SIZE
+    // the renumbered records: the same sizes at the same offsets
+#define SK_YRBIG(X) X(ysc) X(ye2) X(yn_a) X(yn_b) X(yn_c) X(yn_p0) X(yrec) X(yn_w) X(yn_nbp) X(yn_P)
+    P.y_renumbered = yopt.renumber;
+    if (P.y_renumbered) {
+#define SK_SIZE(f) P.r_##f.resize(off_##f[ny]);
+      SK_YRBIG(SK_SIZE)
+#undef SK_SIZE
+    }
     next = 0;
     auto copy = [&]() {
       for (size_t e = next.fetch_add(1); e < ny; e = next.fetch_add(1)) {
@@ -1227,16 +1604,33 @@ int pack_dataset(sk_dataset* ds, std::string& err, const std::function<void()>* 
 #define SK_CPY(f) std::copy(Y.f.begin(), Y.f.end(), P.f.begin() + off_##f[e]);
         SK_YBIG(SK_CPY)
 #undef SK_CPY
+        if (P.y_renumbered) {
+#define SK_CPY(f) std::copy(Y.r.f.begin(), Y.r.f.end(), P.r_##f.begin() + off_##f[e]);
+          SK_YRBIG(SK_CPY)
+#undef SK_CPY
+        }
         Y = YOut();  // free as we go
       }
     };
     run_pool(nthr, copy);
+#undef SK_YRBIG
 #undef SK_YBIG
     if (tstats) {
       long tch = 0;
       for (int32_t c : P.ex_nch) tch += c;
       fprintf(stderr, "[sk pack] y-role %.1f ms (%d threads) + append %.1f ms; sweep chunks %ld (%.2f per y)\n",
               ty1 - tp2, nthr, tnow() - ty1, tch, P.ex_nch.empty() ? 0.0 : (double)tch / P.ex_nch.size());
+    }
+    if (yopt.stats) {  // the sweep's and the MATCH gather's bank model, plain order by length and as packed
+      long tch = 0;
+      for (int32_t c : P.ex_nch) tch += c;
+      const double d = (double)std::max(tch, 1l), g = (double)std::max(mg_groups, 1l);
+      fprintf(stderr,
+              "[sk pack] sweep bank model over %ld chunks: plain order read %.3f atomic %.3f cycles per chunk, "
+              "packed read %.3f atomic %.3f (%ld of %zu y renumbered); MATCH gather read cycles per 64-edge "
+              "group: plain %.3f packed %.3f\n",
+              tch, yc_plain.read / d, yc_plain.atomic / d, yc_now.read / d, yc_now.atomic / d, y_renum, ny,
+              mg_plain / g, mg_now / g);
     }
   }
   return SK_OK;
@@ -1403,17 +1797,19 @@ int sk_dataset_upload(sk_context* ctx, sk_dataset* ds) {
   SK_HIP(ctx, xe);
   const auto tu1 = std::chrono::steady_clock::now();
   D.n_examples = (int32_t)ds->ex.size();
-  SK_HIP(ctx, sk::upload(B, P.yn_a, &D.yn_a));
-  SK_HIP(ctx, sk::upload(B, P.yn_b, &D.yn_b));
-  SK_HIP(ctx, sk::upload(B, P.yn_w, &D.yn_w));
-  SK_HIP(ctx, sk::upload(B, P.yn_nbp, &D.yn_nbp));
-  SK_HIP(ctx, sk::upload(B, P.yn_P, &D.yn_P));
-  SK_HIP(ctx, sk::upload(B, P.ysc, &D.ysc));
-  SK_HIP(ctx, sk::upload(B, P.ye2, &D.ye2));
-  SK_HIP(ctx, sk::upload(B, P.yn_c, &D.yn_c));
-  SK_HIP(ctx, sk::upload(B, P.yn_p0, &D.yn_p0));
+  // the y records the kernel runs: the renumbered ones where they were formed
+  const bool yr = P.y_renumbered;
+  SK_HIP(ctx, sk::upload(B, yr ? P.r_yn_a : P.yn_a, &D.yn_a));
+  SK_HIP(ctx, sk::upload(B, yr ? P.r_yn_b : P.yn_b, &D.yn_b));
+  SK_HIP(ctx, sk::upload(B, yr ? P.r_yn_w : P.yn_w, &D.yn_w));
+  SK_HIP(ctx, sk::upload(B, yr ? P.r_yn_nbp : P.yn_nbp, &D.yn_nbp));
+  SK_HIP(ctx, sk::upload(B, yr ? P.r_yn_P : P.yn_P, &D.yn_P));
+  SK_HIP(ctx, sk::upload(B, yr ? P.r_ysc : P.ysc, &D.ysc));
+  SK_HIP(ctx, sk::upload(B, yr ? P.r_ye2 : P.ye2, &D.ye2));
+  SK_HIP(ctx, sk::upload(B, yr ? P.r_yn_c : P.yn_c, &D.yn_c));
+  SK_HIP(ctx, sk::upload(B, yr ? P.r_yn_p0 : P.yn_p0, &D.yn_p0));
   SK_HIP(ctx, sk::upload(B, P.ycs, &D.ycs));
-  SK_HIP(ctx, sk::upload(B, P.yrec, &D.yrec));
+  SK_HIP(ctx, sk::upload(B, yr ? P.r_yrec : P.yrec, &D.yrec));
   SK_HIP(ctx, sk::upload(B, P.ex_ysc_base, &D.ex_ysc_base));
   SK_HIP(ctx, sk::upload(B, P.ex_nch, &D.ex_nch));
   SK_HIP(ctx, sk::upload(B, P.ex_ycs_base, &D.ex_ycs_base));
@@ -1436,6 +1832,71 @@ int sk_dataset_upload(sk_context* ctx, sk_dataset* ds) {
                  "%.1f MB in all, y-role transfer %.1f ms\n",
                  std::chrono::duration<double, std::milli>(tu1 - tu0).count(), x_ms, B.ptrs.size(), B.bytes / 1e6,
                  std::chrono::duration<double, std::milli>(tu2 - tu1).count());
+  }
+  return SK_OK;
+}
+
+int sk_dataset_sweep_conflicts(const sk_dataset* ds, int i, int32_t* read_cycles, int32_t* atomic_cycles,
+                               int32_t* chunks) {
+  if (!ds) return SK_ERR_INVALID;
+  if (i < 0 || i >= (int)ds->ex.size()) return SK_ERR_RANGE;
+  const sk::HostPack& P = ds->pack;
+  if (P.ex_nch.size() != ds->ex.size()) return SK_ERR_INVALID;  // not packed yet
+  long rd = 0, at = 0;
+  for (int c = 0; c < P.ex_nch[i]; ++c) {
+    int r1, a1;
+    sk::sweep_chunk_cost(P.run_ysc().data() + ((size_t)P.ex_ysc_base[i] + c) * 64, &r1, &a1);
+    rd += r1;
+    at += a1;
+  }
+  if (read_cycles) *read_cycles = (int32_t)rd;
+  if (atomic_cycles) *atomic_cycles = (int32_t)at;
+  if (chunks) *chunks = P.ex_nch[i];
+  return SK_OK;
+}
+
+int sk_dataset_y_role(const sk_dataset* ds, int i, int plain, int32_t* n_nodes, int32_t* n_edges, int32_t* n_chunks,
+                      int32_t* max_len, uint32_t* node, uint32_t* len, uint32_t* edges, uint32_t* sweep,
+                      int32_t* first_chunk, int32_t* cost) {
+  if (!ds) return SK_ERR_INVALID;
+  if (i < 0 || i >= (int)ds->ex.size()) return SK_ERR_RANGE;
+  if (sk::ds_pal(ds) || sk::ds_protein(ds)) return SK_ERR_INVALID;
+  try {
+    // the example packed alone: its x-role node records (no key tables: they
+    // do not enter the y role), then its y role in the order asked for
+    sk::XOut O;
+    sk::pack_x(ds->ex[i], sk::KeyTables(), O);
+    if (O.rc) return O.rc;
+    sk::HostPack P;
+#define SK_MV(f) P.f.assign(O.f.begin(), O.f.end());
+    SK_MV(nd_a) SK_MV(nd_b) SK_MV(nd_c) SK_MV(nd_w) SK_MV(nd_nbp) SK_MV(nd_P) SK_MV(ed) SK_MV(bpf_code) SK_MV(bpf_p)
+#undef SK_MV
+    sk::YOpts opt;
+    const char* lanes_env = SK_KNOB("SK_SWEEP_LANES");
+    opt.sweep_lanes_greedy = !lanes_env || std::atoi(lanes_env) != 0;
+    opt.renumber = !plain && !SK_KNOB("SK_NO_Y_RENUMBER");
+    sk::YOut Y;
+    sk::pack_y(P, opt, sk::YJob{0, 0, 0, O.nl, O.big}, Y);
+    if (!Y.err.empty()) return SK_ERR_INVALID;
+    const sk::YRec& R = opt.renumber ? Y.r : Y;
+    if (n_nodes) *n_nodes = O.nl;
+    if (n_edges) *n_edges = (int32_t)R.ye2.size();
+    if (n_chunks) *n_chunks = Y.nch;
+    if (max_len) *max_len = (int32_t)Y.ycs.size() - 2;
+    if (node) std::copy(R.src.begin(), R.src.end(), node);
+    if (len)
+      for (int k = 0; k < O.nl; ++k) len[k] = R.yn_b[k] & 0xffff;
+    if (edges) std::copy(R.ye2.begin(), R.ye2.end(), edges);
+    if (sweep) std::copy(R.ysc.begin(), R.ysc.end(), sweep);
+    if (first_chunk) std::copy(Y.ycs.begin(), Y.ycs.end(), first_chunk);
+    if (cost) {
+      cost[0] = (int32_t)(opt.renumber ? Y.cost : Y.cost_plain).read;
+      cost[1] = (int32_t)(opt.renumber ? Y.cost : Y.cost_plain).atomic;
+      cost[2] = (int32_t)Y.cost_plain.read;
+      cost[3] = (int32_t)Y.cost_plain.atomic;
+    }
+  } catch (const std::bad_alloc&) {
+    return SK_ERR_ALLOC;
   }
   return SK_OK;
 }
@@ -1481,6 +1942,7 @@ int sk_dataset_pack_digest(sk_dataset* ds, uint64_t* y_hash, uint64_t* x_hash) {
 #define SK_DG_Y(f) hy = hv(P.f, hy);
 #define SK_DG_X(f) hx = hv(P.f, hx);
   SK_PACK_Y_ARRAYS(SK_DG_Y)
+  SK_PACK_YR_ARRAYS(SK_DG_Y)
   SK_PACK_X_ARRAYS(SK_DG_X)
 #undef SK_DG_Y
 #undef SK_DG_X

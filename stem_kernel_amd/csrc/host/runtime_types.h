@@ -108,6 +108,17 @@ struct HostPack {
   pvec<double> yn_P;
   pvec<int32_t> ycs;
   std::vector<int32_t> ex_ysc_base, ex_nch, ex_ycs_base;
+  // the same y records with the equal-length nodes renumbered for the LDS
+  // banks (host/pack.cpp renumber_equal_lengths), at the same offsets, in
+  // arrays of their own (the ones above stay the plain stable order by
+  // length); empty unless y_renumbered, which also says that the device image
+  // holds them as its y records
+  pvec<uint32_t> r_yn_a, r_yn_b, r_yn_c, r_ye2, r_ysc;
+  pvec<uint4> r_yrec;
+  pvec<float> r_yn_w, r_yn_nbp, r_yn_p0;
+  pvec<double> r_yn_P;
+  bool y_renumbered = false;
+  const pvec<uint32_t>& run_ysc() const { return y_renumbered ? r_ysc : ysc; }
   pvec<uint32_t> xr_node, xr_ch;
   // gamma schedule (device_set.h): the x rows without the gamma rows, the
   // gamma rows' K inputs, the dataset's gamma keys and the y gapless flags
@@ -154,6 +165,9 @@ struct HostPack {
 // sk_dataset_pack_digest and tools/pack_compare.cpp hash them in this order
 #define SK_PACK_Y_ARRAYS(X) X(yn_a) X(yn_b) X(yn_c) X(ye2) X(ysc) X(yrec) X(yn_w) X(yn_nbp) X(yn_p0) X(yn_P) \
   X(ycs) X(ex_ysc_base) X(ex_nch) X(ex_ycs_base)
+// the renumbered y records (hashed after the list above, which tools/pack_compare.cpp pins)
+#define SK_PACK_YR_ARRAYS(X) X(r_yn_a) X(r_yn_b) X(r_yn_c) X(r_ye2) X(r_ysc) X(r_yrec) X(r_yn_w) X(r_yn_nbp) \
+  X(r_yn_p0) X(r_yn_P)
 #define SK_PACK_X_ARRAYS(X) X(nd_a) X(nd_b) X(nd_c) X(nd_w) X(nd_nbp) X(nd_P) X(ed) X(bpf_code) X(bpf_p)     \
   X(lvl) X(xr_ch) X(xrow) X(xr_node) X(gr_info) X(gr_pf) X(gr_P) X(xg_ch) X(xg_clg) X(xg_cpf) X(xg_cty)     \
   X(phk_idx) X(gra_gidx) X(gra_row) X(xgrow) X(xg_node) X(pos_prof) X(pos_w) X(pos_chr) X(pos_lru)          \

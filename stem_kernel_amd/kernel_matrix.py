@@ -605,6 +605,38 @@ class Dataset:
         return dict(zip(("rows", "stored", "slab_reads", "gamma_reads", "phi_reads", "reg_reads",
                          "y_slots"), (a.value for a in v)))
 
+    def sweep_conflicts(self, i: int) -> dict:
+        """LDS bank model of example i's IY sweep as packed: read cycles,
+        atomic cycles and chunks (sk_dataset_sweep_conflicts; the dataset must
+        be uploaded)."""
+        v = [C.c_int32() for _ in range(3)]
+        check(lib().sk_dataset_sweep_conflicts(self._h, i, *[C.byref(a) for a in v]))
+        return dict(zip(("read_cycles", "atomic_cycles", "chunks"), (a.value for a in v)))
+
+    def y_role(self, i: int, plain: bool = False) -> dict:
+        """The y role of example i packed alone on the host, in the packer's
+        numbering or (plain) the plain stable order by length
+        (sk_dataset_y_role): node, len, edges, sweep [chunks][64],
+        first_chunk, and the sweep's bank-model cost of this order and of the
+        plain one."""
+        n = [C.c_int32() for _ in range(4)]
+        null_u, null_i = C.POINTER(C.c_uint32)(), C.POINTER(C.c_int32)()
+        check(lib().sk_dataset_y_role(self._h, i, int(plain), *[C.byref(a) for a in n], null_u, null_u, null_u,
+                                      null_u, null_i, null_i))
+        nl, ne, nch, lmax = (a.value for a in n)
+        u = lambda k: np.zeros(max(k, 1), np.uint32)
+        d = dict(node=u(nl), len=u(nl), edges=u(ne), sweep=u(64 * nch), first_chunk=np.zeros(lmax + 2, np.int32),
+                 cost=np.zeros(4, np.int32))
+        ptr = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint32 if a.dtype == np.uint32 else C.c_int32))
+        check(lib().sk_dataset_y_role(self._h, i, int(plain), *[C.byref(a) for a in n],
+                                      *[ptr(d[k]) for k in ("node", "len", "edges", "sweep", "first_chunk", "cost")]))
+        cost = d.pop("cost")
+        out = dict(node=d["node"][:nl], len=d["len"][:nl], edges=d["edges"][:ne],
+                   sweep=d["sweep"][:64 * nch].reshape(nch, 64), first_chunk=d["first_chunk"])
+        out.update(read_cycles=int(cost[0]), atomic_cycles=int(cost[1]), plain_read_cycles=int(cost[2]),
+                   plain_atomic_cycles=int(cost[3]))
+        return out
+
     def shared_sums(self, i: int):
         """(shared-sum rows, member records they replaced) of example i in the
         factored gamma schedule (sk_dataset_shared_sums; uploaded datasets)."""
