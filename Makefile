@@ -19,7 +19,7 @@ HOST_SRC := $(ROOT)stem_kernel_amd/csrc/host/synth.cpp $(ROOT)stem_kernel_amd/cs
             $(ROOT)stem_kernel_amd/csrc/host/svm_train.cpp $(ROOT)stem_kernel_amd/csrc/host/auc_gradient.cpp \
             $(ROOT)stem_kernel_amd/csrc/host/feature_gram.cpp
 # the host runtime behind the ABI (they share host/runtime.h, host/runtime_types.h)
-API_SRC := $(ROOT)stem_kernel_amd/csrc/sk_api.cpp $(addprefix $(ROOT)stem_kernel_amd/csrc/host/,context.cpp pack.cpp pack_shared_sums.cpp \
+API_SRC := $(ROOT)stem_kernel_amd/csrc/sk_api.cpp $(addprefix $(ROOT)stem_kernel_amd/csrc/host/,context.cpp pack.cpp pack_x.cpp pack_y.cpp pack_sweep.cpp pack_shared_sums.cpp \
            dataset.cpp dataset_io.cpp fold_gpu.cpp pairs_dag.cpp pairs_bpla.cpp pairs_la_protein.cpp \
            pairs_simpal.cpp pairs_stem4d.cpp la_protein_grad.cpp stem_grad.cpp pairs_stem_grad.cpp)
 HIP_SRC := $(ROOT)stem_kernel_amd/csrc/kernels/dag_stem.hip $(ROOT)stem_kernel_amd/csrc/kernels/profile_string.hip \

@@ -109,7 +109,7 @@ struct HostPack {
   pvec<int32_t> ycs;
   std::vector<int32_t> ex_ysc_base, ex_nch, ex_ycs_base;
   // the same y records with the equal-length nodes renumbered for the LDS
-  // banks (host/pack.cpp renumber_equal_lengths), at the same offsets, in
+  // banks (host/pack_sweep.cpp renumber_equal_lengths), at the same offsets, in
   // arrays of their own (the ones above stay the plain stable order by
   // length); empty unless y_renumbered, which also says that the device image
   // holds them as its y records
@@ -157,24 +157,31 @@ struct HostPack {
   const std::vector<int32_t>& run_nl() const { return shared_sums ? ex_nlxf : ex_nlxg; }
   const std::vector<int32_t>& run_ch_base() const { return shared_sums ? ex_xfch_base : ex_xgch_base; }
 };
-// the factored schedule's arrays (hashed apart from the lists below)
-#define SK_PACK_F_ARRAYS(X) X(xf_row) X(xf_node) X(xf_ch) X(xf_clg) X(xf_cpf) X(xf_cty) X(xf_gra_row) \
-  X(ex_xf_base) X(ex_nlxf) X(ex_xfch_base) X(ex_ss_rows) X(ex_ss_repl)
-// every packed array: the y-role records (SK_YBIG and their bases) and the
-// x-role / per-example arrays (SK_BIG, the ex_* vectors, the key tables) --
-// sk_dataset_pack_digest and tools/pack_compare.cpp hash them in this order
-#define SK_PACK_Y_ARRAYS(X) X(yn_a) X(yn_b) X(yn_c) X(ye2) X(ysc) X(yrec) X(yn_w) X(yn_nbp) X(yn_p0) X(yn_P) \
-  X(ycs) X(ex_ysc_base) X(ex_nch) X(ex_ycs_base)
-// the renumbered y records (hashed after the list above, which tools/pack_compare.cpp pins)
-#define SK_PACK_YR_ARRAYS(X) X(r_yn_a) X(r_yn_b) X(r_yn_c) X(r_ye2) X(r_ysc) X(r_yrec) X(r_yn_w) X(r_yn_nbp) \
-  X(r_yn_p0) X(r_yn_P)
-#define SK_PACK_X_ARRAYS(X) X(nd_a) X(nd_b) X(nd_c) X(nd_w) X(nd_nbp) X(nd_P) X(ed) X(bpf_code) X(bpf_p)     \
+// Every packed array, named once.  The *_CAT lists are the arrays that
+// pack_x / pack_y form per example and pack_dataset concatenates (host/pack.cpp:
+// one offset vector, one resize and one copy per name); a list without CAT
+// is its CAT part followed by the per-example scalars, bases and key tables.
+// sk_dataset_pack_digest and tools/pack_compare.cpp hash the lists in this
+// order, which the pinned hashes fix.
+// the y records that depend on the numbering of the nodes, under the prefix p
+// (none: the plain stable order by length; r_: the renumbered ones)
+#define SK_PACK_YREC_ARRAYS(X, p) X(p##yn_a) X(p##yn_b) X(p##yn_c) X(p##ye2) X(p##ysc) X(p##yrec) X(p##yn_w) \
+  X(p##yn_nbp) X(p##yn_p0) X(p##yn_P)
+#define SK_PACK_Y_CAT_ARRAYS(X) SK_PACK_YREC_ARRAYS(X, ) X(ycs)
+#define SK_PACK_Y_ARRAYS(X) SK_PACK_Y_CAT_ARRAYS(X) X(ex_ysc_base) X(ex_nch) X(ex_ycs_base)
+#define SK_PACK_YR_ARRAYS(X) SK_PACK_YREC_ARRAYS(X, r_)
+#define SK_PACK_X_CAT_ARRAYS(X) X(nd_a) X(nd_b) X(nd_c) X(nd_w) X(nd_nbp) X(nd_P) X(ed) X(bpf_code) X(bpf_p) \
   X(lvl) X(xr_ch) X(xrow) X(xr_node) X(gr_info) X(gr_pf) X(gr_P) X(xg_ch) X(xg_clg) X(xg_cpf) X(xg_cty)     \
   X(phk_idx) X(gra_gidx) X(gra_row) X(xgrow) X(xg_node) X(pos_prof) X(pos_w) X(pos_chr) X(pos_lru)          \
-  X(ex_phi_bits) X(ex_nl) X(ex_node_base) X(ex_edge_base) X(ex_bpf_base) X(ex_lvl_base) X(ex_nlev) X(ex_len) \
-  X(ex_pos_base) X(ex_has_w) X(ex_dyadic) X(ex_str_fast) X(ex_onehot) X(ex_big) X(ex_nseqs) X(ex_nslots)    \
-  X(ex_xch_base) X(gam_key) X(ex_xg_base) X(ex_nlxg) X(ex_xgch_base) X(ex_gr_base) X(ex_gapless) X(phi_al)   \
-  X(phi_g) X(ex_gra_base) X(ex_phk_base)
+  X(ex_phi_bits)
+#define SK_PACK_X_ARRAYS(X) SK_PACK_X_CAT_ARRAYS(X) X(ex_nl) X(ex_node_base) X(ex_edge_base) X(ex_bpf_base) \
+  X(ex_lvl_base) X(ex_nlev) X(ex_len) X(ex_pos_base) X(ex_has_w) X(ex_dyadic) X(ex_str_fast) X(ex_onehot)   \
+  X(ex_big) X(ex_nseqs) X(ex_nslots) X(ex_xch_base) X(gam_key) X(ex_xg_base) X(ex_nlxg) X(ex_xgch_base)     \
+  X(ex_gr_base) X(ex_gapless) X(phi_al) X(phi_g) X(ex_gra_base) X(ex_phk_base)
+// the factored schedule's arrays (hashed apart from the lists above)
+#define SK_PACK_F_CAT_ARRAYS(X) X(xf_row) X(xf_node) X(xf_ch) X(xf_clg) X(xf_cpf) X(xf_cty) X(xf_gra_row)
+#define SK_PACK_F_ARRAYS(X) SK_PACK_F_CAT_ARRAYS(X) X(ex_xf_base) X(ex_nlxf) X(ex_xfch_base) X(ex_ss_rows) \
+  X(ex_ss_repl)
 
 // 4-D stem kernel tables of every example of a dataset, resident on the
 // device: one set per (device, bp model, loop), built on the first 4-D call
@@ -462,7 +469,8 @@ struct Arena {
 };
 
 // ------------------------------------------------------------ across files
-// the packer (host/pack.cpp; tools/pack_compare.cpp times it) and one
+// the packer (host/pack.cpp, over the per-example passes that
+// host/pack_internal.h declares; tools/pack_compare.cpp times it) and one
 // position's BPLA weights as it forms them (sk_dataset_bpla_weights)
 int pack_dataset(sk_dataset* ds, std::string& err, const std::function<void()>* after_x = nullptr);
 float4 bpla_weight(const Example& X, int i);

@@ -20,6 +20,8 @@ _SRC_DIRS = ("stem_kernel_amd/csrc/kernels",)
 _SRC_FILES = ("stem_kernel_amd/csrc/sk_api.cpp", "stem_kernel_amd/csrc/host/runtime.h",
               "stem_kernel_amd/csrc/host/runtime_types.h", "stem_kernel_amd/csrc/host/pairs_dag.cpp",
               "stem_kernel_amd/csrc/host/context.cpp", "stem_kernel_amd/csrc/host/pack.cpp",
+              "stem_kernel_amd/csrc/host/pack_x.cpp", "stem_kernel_amd/csrc/host/pack_y.cpp",
+              "stem_kernel_amd/csrc/host/pack_sweep.cpp", "stem_kernel_amd/csrc/host/pack_internal.h",
               "stem_kernel_amd/csrc/host/dataset.cpp", "stem_kernel_amd/csrc/host/dataset_io.cpp",
               "stem_kernel_amd/csrc/host/fold_gpu.cpp", "stem_kernel_amd/csrc/host/pairs_bpla.cpp",
               "stem_kernel_amd/csrc/host/pairs_la_protein.cpp", "stem_kernel_amd/csrc/host/pairs_simpal.cpp",

@@ -227,7 +227,7 @@ def probe_kernel(variant, g):
 
 def categories(ds, has_w):
     """Per ordered pair the kernel that takes it (0 one-hot, 1 dyadic, 2
-    general), by the rules of pack.cpp / pairs_dag.cpp restated on the
+    general), by the rules of pack_x.cpp / pairs_dag.cpp restated on the
     profiles the dataset holds."""
     oh, fast = [], []
     for k in range(len(ds)):

@@ -1,13 +1,18 @@
-"""The dataset packing (host/pack.cpp pack_dataset) runs its per-example passes
-on host threads and appends at prefix offsets: the packed arrays must not
-depend on the thread count.  tools/pack_compare.cpp calls the library's
-sk::pack_dataset (host/runtime_types.h) and hashes every packed array (the
-y-role records, every SK_BIG x-role array, the per-example ex_* vectors and
-key tables); it is built here (host code only, at -O1: the packer it runs is
-the library's, built as shipped) and run with one thread and with eight
-(SK_PACK_THREADS), and both must equal GOLDEN: the hashes of the serial packer before the threaded one
-(commit 61ba1f6^, built in a worktree with this pack_compare.cpp, r05), so a
-rebase bug that does not depend on the thread count fails here too."""
+"""The dataset packing (host/pack.cpp pack_dataset, over pack_x.cpp, pack_y.cpp
+and pack_sweep.cpp) runs its per-example passes on host threads and appends
+at prefix offsets: the packed arrays must not depend on the thread count.
+tools/pack_compare.cpp calls the library's sk::pack_dataset
+(host/runtime_types.h) and hashes every packed array, one hash per list of
+runtime_types.h: y (the y-role records in the plain order), x (the x-role
+arrays, the per-example ex_* vectors and key tables), r (the renumbered y
+records) and f (the factored gamma schedule) -- r and f are what the device
+runs.  It is built here (host code only, at -O1: the packer it runs is the
+library's, built as shipped) and run with one thread and with eight
+(SK_PACK_THREADS), and both must equal GOLDEN.  Its y and x values are the
+hashes of the serial packer before the threaded one (commit 61ba1f6^, built
+in a worktree with this pack_compare.cpp), its r and f values those of the
+one-file packer before it was split (commit 9b92a18, built likewise), so a
+bug that does not depend on the thread count fails here too."""
 import os
 import subprocess
 
@@ -27,9 +32,9 @@ def pack_compare(tmp_path_factory):
     return exe
 
 
-GOLDEN = {(300, 150): ("36d6bd2e8250904e", "287b3489cc46be35"),
-          (64, 300): ("88c43b92757d6d0c", "7683c19231feea38"),
-          (7, 40): ("5103f9f17bc7fe14", "f110ddedec494801")}
+GOLDEN = {(300, 150): ("36d6bd2e8250904e", "287b3489cc46be35", "d97d6b913fcd5c64", "5466fe1e49a0330c"),
+          (64, 300): ("88c43b92757d6d0c", "7683c19231feea38", "38d1453624e9121a", "4a46b469eccad71e"),
+          (7, 40): ("5103f9f17bc7fe14", "f110ddedec494801", "9c80d80bf46f9050", "4391e0ff1458cbc0")}
 
 
 @pytest.mark.parametrize("n,L", sorted(GOLDEN))
@@ -39,6 +44,5 @@ def test_packing_independent_of_threads(pack_compare, n, L):
                            capture_output=True, text=True, timeout=300, check=True)
         line = r.stdout.strip().splitlines()[-1]
         assert line.startswith("rc=0"), line
-        hy = line.split("y-hash ")[1].split()[0]
-        hx = line.split("x-hash ")[1].split()[0]
-        assert (hy, hx) == GOLDEN[(n, L)], (t, hy, hx)
+        got = tuple(line.split(f" {k}-hash ")[1].split()[0] for k in "yxrf")
+        assert got == GOLDEN[(n, L)], (t, got)

@@ -1,4 +1,4 @@
-"""The DAG stem kernel on y's numbered by the renumbering pass (host/pack.cpp
+"""The DAG stem kernel on y's numbered by the renumbering pass (host/pack_sweep.cpp
 renumber_equal_lengths; the packed arrays themselves:
 tests/test_y_renumber_cpu.py).  Every ordered pair of each set is computed
 

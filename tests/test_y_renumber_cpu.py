@@ -1,5 +1,5 @@
-"""The y-role numbering of the DAG stem kernel (host/pack.cpp pack_y,
-renumber_equal_lengths): nodes are numbered by length, and the
+"""The y-role numbering of the DAG stem kernel (host/pack_y.cpp pack_y,
+host/pack_sweep.cpp renumber_equal_lengths): nodes are numbered by length, and the
 order inside a run of equal lengths -- which fixes only a node's LDS bank, id
 mod 32 as a child read and id mod 16 as an atomic target -- is chosen to lower
 the bank model of the IY sweep's chunks (SweepBanks).  Host only, through

@@ -1,6 +1,7 @@
 // Host packing check (CPU only): packs a synthetic dataset with the
-// sk::pack_dataset of the library it links (host/pack.cpp) and prints the
-// hashes of the packed arrays and the pack time.  To compare two versions,
+// sk::pack_dataset of the library it links (host/pack.cpp over pack_x.cpp,
+// pack_y.cpp and pack_sweep.cpp) and prints the hashes of the packed arrays,
+// one per list of host/runtime_types.h, and the pack time.  To compare two versions,
 // build each version's own tools/pack_compare.cpp in its tree against that
 // tree's library (make lib) and run both, e.g.
 //   git worktree add /tmp/old OLD && make -C /tmp/old lib
@@ -42,12 +43,18 @@ int main(int argc, char** argv) {
   rc |= pack_dataset(ds, err);
   auto t2 = std::chrono::steady_clock::now();
   const HostPack& P = ds->pack;
-  uint64_t h = 1469598103934665603ull, hx = h;
+  uint64_t h = 1469598103934665603ull, hx = h, hr = h, hf = h;
   const bool each = std::getenv("PC_EACH") != nullptr;  // one line per array (bisecting a mismatch)
-#define PC_HY(f) h = hv(P.f, h); if (each) printf("  %s %016llx\n", #f, (unsigned long long)hv(P.f, 1469598103934665603ull));
-#define PC_HX(f) hx = hv(P.f, hx); if (each) printf("  %s %016llx\n", #f, (unsigned long long)hv(P.f, 1469598103934665603ull));
+#define PC_H(acc, f) acc = hv(P.f, acc); if (each) printf("  %s %016llx\n", #f, (unsigned long long)hv(P.f, 1469598103934665603ull));
+#define PC_HY(f) PC_H(h, f)
+#define PC_HX(f) PC_H(hx, f)
+#define PC_HR(f) PC_H(hr, f)
+#define PC_HF(f) PC_H(hf, f)
   SK_PACK_Y_ARRAYS(PC_HY)
   SK_PACK_X_ARRAYS(PC_HX)
-  printf("rc=%d n=%d L=%d pack %.3f s  y-hash %016llx  x-hash %016llx max_nch %d\n", rc, n, L,
-         std::chrono::duration<double>(t2 - t1).count(), (unsigned long long)h, (unsigned long long)hx, P.max_nch);
+  SK_PACK_YR_ARRAYS(PC_HR)  // what the device runs: the renumbered y records, the factored schedule
+  SK_PACK_F_ARRAYS(PC_HF)
+  printf("rc=%d n=%d L=%d pack %.3f s  y-hash %016llx  x-hash %016llx  r-hash %016llx  f-hash %016llx max_nch %d\n",
+         rc, n, L, std::chrono::duration<double>(t2 - t1).count(), (unsigned long long)h, (unsigned long long)hx,
+         (unsigned long long)hr, (unsigned long long)hf, P.max_nch);
 }
