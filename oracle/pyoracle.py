@@ -81,6 +81,13 @@ def oracle():
         L.orc_stem4d_partial.argtypes = [C.c_char_p, _D, C.c_char_p, _D, C.c_double, C.c_double,
                                          C.c_double, C.c_float, C.c_int, C.c_uint, C.c_uint,
                                          C.c_float, C.c_int]
+        for n in ("orc_stem4d_gen", "orc_stem4d_partial_ld"):
+            getattr(L, n).restype = C.c_double
+            getattr(L, n).argtypes = [C.c_char_p, _D, C.c_char_p, _D, C.c_double, C.c_double,
+                                      C.c_double, C.c_float, C.c_int, C.c_uint, C.c_uint, C.c_int]
+        L.orc_stem4d_ld.restype = C.c_double
+        L.orc_stem4d_ld.argtypes = [C.c_char_p, _D, C.c_char_p, _D, C.c_double, C.c_double,
+                                    C.c_double, C.c_float, C.c_int, C.c_uint, C.c_int]
         L.orc_phmm_posterior.restype = C.c_int
         L.orc_phmm_posterior.argtypes = [C.c_char_p, C.c_char_p, C.c_int, _D]
         L.orc_alignment_constraints.restype = C.c_int
@@ -562,6 +569,35 @@ def stem4d(x: str, bpx, y: str, bpy, gap=0.8, stack=1.0, subst=0.5, bp_bound=0.0
                                           bp_bound, model, loop, band)
     return oracle().orc_stem4d(x.encode(), px, y.encode(), py, gap, stack, subst, bp_bound,
                                model, loop)
+
+
+def _bpp_args(bpx, bpy):
+    keep = [np.ascontiguousarray(b, dtype=np.float64) if b is not None else None for b in (bpx, bpy)]
+    return keep, [k.ctypes.data_as(_D) if k is not None and k.size else None for k in keep]
+
+
+def stem4d_ld(x: str, bpx, y: str, bpy, gap=0.8, stack=1.0, subst=0.5, bp_bound=0.0, model=0,
+              loop=3, band=0, cut=-1) -> float:
+    """stem4d() without -a (full_dp, or partial_dp under the -b band) with
+    every product and sum in long double, rounded to double once
+    (oracle/stem4d_generic.inc).  cut >= 0: the two base terms G0 = g^(l-k) and
+    g^(j-i) are zero beyond cut positions (the visibility tests' emulation of
+    a truncated gap-power table); cut < 0 is the DP itself."""
+    keep, (px, py) = _bpp_args(bpx, bpy)
+    if band:
+        return oracle().orc_stem4d_partial_ld(x.encode(), px, y.encode(), py, gap, stack, subst,
+                                              bp_bound, model, loop, band, cut)
+    return oracle().orc_stem4d_ld(x.encode(), px, y.encode(), py, gap, stack, subst, bp_bound,
+                                  model, loop, cut)
+
+
+def stem4d_gen(x: str, bpx, y: str, bpy, gap=0.8, stack=1.0, subst=0.5, bp_bound=0.0, model=0,
+               loop=3, band=0, cut=-1) -> float:
+    """The double instantiation of stem4d_ld()'s generic body: stem4d() bit
+    for bit when cut < 0 (tests/test_stem4d_oracle_twin.py)."""
+    keep, (px, py) = _bpp_args(bpx, bpy)
+    return oracle().orc_stem4d_gen(x.encode(), px, y.encode(), py, gap, stack, subst, bp_bound,
+                                   model, loop, band, cut)
 
 
 def stem4d_ksum(x: str, bpx, y: str, bpy, gap=0.8, stack=1.0, subst=0.5, bp_bound=0.0, model=0,

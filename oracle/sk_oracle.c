@@ -1719,3 +1719,39 @@ double orc_stem4d_partial(const char *x, const double *bpx, const char *y, const
   free(gpw);
   return result;
 }
+
+/* ------------------------------------------------------------------ */
+/* Twins of the two 4-D DPs above for the 4-D kernels' tests
+ * (stem4d_generic.inc): full_dp (band 0) and partial_dp under the -b band in
+ * double (_gen, bit for bit the pinned functions when cut < 0) and in long
+ * double rounded to double once (_ld).  cut >= 0 truncates the two base
+ * terms (the visibility tests' emulation of a cut-off gap-power table).
+ * stem4d_full and orc_stem4d_partial themselves stay as pinned. */
+#define REAL double
+#define SUFFIX(n) n##_d
+#include "stem4d_generic.inc"
+#undef REAL
+#undef SUFFIX
+#define REAL long double
+#define SUFFIX(n) n##_ld
+#include "stem4d_generic.inc"
+#undef REAL
+#undef SUFFIX
+
+double orc_stem4d_gen(const char *x, const double *bpx, const char *y, const double *bpy,
+                      double gap, double stack, double subst, float bp_bound, int model,
+                      unsigned loop, unsigned band, int cut) {
+  return stem4d_dp_d(x, bpx, y, bpy, gap, stack, subst, bp_bound, model, loop, band, cut);
+}
+
+double orc_stem4d_ld(const char *x, const double *bpx, const char *y, const double *bpy,
+                     double gap, double stack, double subst, float bp_bound, int model,
+                     unsigned loop, int cut) {
+  return stem4d_dp_ld(x, bpx, y, bpy, gap, stack, subst, bp_bound, model, loop, 0, cut);
+}
+
+double orc_stem4d_partial_ld(const char *x, const double *bpx, const char *y, const double *bpy,
+                             double gap, double stack, double subst, float bp_bound, int model,
+                             unsigned loop, unsigned band, int cut) {
+  return stem4d_dp_ld(x, bpx, y, bpy, gap, stack, subst, bp_bound, model, loop, band, cut);
+}

@@ -159,6 +159,22 @@ void orc_stem4d_band(int n, int m, unsigned band, unsigned *c_low, unsigned *c_h
 double orc_stem4d_partial(const char *x, const double *bpx, const char *y, const double *bpy,
                           double gap, double stack, double subst, float bp_bound, int model,
                           unsigned loop, unsigned band, float ali_bound, int zerop_fixed);
+/* Twins of orc_stem4d / orc_stem4d_banded for the 4-D kernels' tests
+ * (stem4d_generic.inc): the same inputs and the same order of operations in
+ * double (_gen: band 0 = full_dp, band > 0 = partial_dp under the -b band;
+ * bit for bit the two functions above when cut < 0) and in long double,
+ * rounded to double once (_ld, _partial_ld).  cut >= 0 zeroes the base terms
+ * G0 = g^(l-k) of the (j,j) planes beyond l - k = cut and g^(j-i) of the
+ * diagonal cells beyond j - i = cut (a truncated gap-power table). */
+double orc_stem4d_gen(const char *x, const double *bpx, const char *y, const double *bpy,
+                      double gap, double stack, double subst, float bp_bound, int model,
+                      unsigned loop, unsigned band, int cut);
+double orc_stem4d_ld(const char *x, const double *bpx, const char *y, const double *bpy,
+                     double gap, double stack, double subst, float bp_bound, int model,
+                     unsigned loop, int cut);
+double orc_stem4d_partial_ld(const char *x, const double *bpx, const char *y, const double *bpy,
+                             double gap, double stack, double subst, float bp_bound, int model,
+                             unsigned loop, unsigned band, int cut);
 /* PairHMM posteriors fw*bk/w (phmm.cpp:10-115): fb[s][i][j], s = M, IX, IY,
  * 3*(|x|+1)*(|y|+1) doubles.  -1 on a non-ACGU residue. */
 int orc_phmm_posterior(const char *x, const char *y, int zerop_fixed, double *fb);

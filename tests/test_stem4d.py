@@ -1,5 +1,9 @@
 """4-D stem kernel (stem_kernel/): oracle anchors on CPU,
-HIP parity (1e-6 relative, double) on the GPU.
+HIP parity on the GPU: full_dp and -b against the oracle's long-double twin
+within the tolerance derived from the DP's roundings (tests/stem4d_probes.py,
+DESIGN.md §7.3; a few 1e-10 at L = 70, 4e-9 at L = 130), the -a option against
+the oracle at 1e-6 relative (its constraints are discrete decisions of the
+PairHMM).
 
 Parity anchors: the reference's CLI default without Vienna runs
 NormalBasePair with bp_bound 1.0, which makes every kernel value 1
@@ -11,9 +15,21 @@ import pytest
 
 import stem_kernel_amd as ska
 from oracle import pyoracle as po
+from tests import stem4d_probes as sp
 from tests.helpers import make_examples, rel_err
 
-TOL = 1e-6
+TOL = 1e-6   # the -a tests
+
+
+def _twin_check(got, seqs, kern, pairs, ref=None):
+    """got[k] = K(seqs[a], seqs[b]) of the pairs against the long-double twin
+    (live, or ref from the golden file) within the derived tolerance."""
+    pairs = [(int(a), int(b)) for a, b in pairs]
+    ref = sp.twin_values(seqs, pairs, kern.params) if ref is None else ref
+    worst, rel, top = sp.excess(np.asarray(got).ravel(), ref, sp.pair_tols(seqs, pairs, kern.params))
+    print(f"largest relative error {rel:.3g}, tolerance {top:.3g}, error / tolerance {worst:.3g}")
+    assert top <= sp.DENSE_CAP, top   # (every set of this file also in test_stem4d_visibility_cpu.py)
+    assert worst <= 1.0, (rel, top)
 
 
 def _seqs():
@@ -76,8 +92,7 @@ def test_stem4d_gram_matches_oracle(gpu_ctx, model, bound):
     got = gpu_ctx.gram(ds, kern)
     n = len(seqs)
     iu = list(zip(*np.triu_indices(n)))
-    ref = _oracle(seqs, kern, iu)
-    assert rel_err(got[tuple(np.array(iu).T)], ref) < TOL
+    _twin_check(got[tuple(np.array(iu).T)], seqs, kern, iu)
     if model == 1 and bound == 1.0:
         assert np.all(got == 1.0)
 
@@ -94,8 +109,8 @@ def test_stem4d_col_default_oracle(gpu_ctx):
     assert gpu_ctx.last_classes()["stem4d_col"]
     n = len(seqs)
     iu = list(zip(*np.triu_indices(n)))
-    ref = _oracle(seqs, kern, iu)
-    assert rel_err(a[tuple(np.array(iu).T)], ref) < TOL
+    assert tuple(seqs) == sp.dense_set("col")[0]
+    _twin_check(a[tuple(np.array(iu).T)], seqs, kern, iu, sp.dense_ref("col", 0.8, 0))
     assert a[n - 4, n - 4] == 1.0 and np.all(a[n - 4, :] == 1.0)  # the empty sequence: K = 1
 
 
@@ -125,8 +140,8 @@ def test_stem4d_ksum_equals_four_state(gpu_ctx, monkeypatch, mode):
     assert rel_err(a, b) < 1e-12
     n = len(seqs)
     iu = list(zip(*np.triu_indices(n)))
-    ref = _oracle(seqs, kern, iu)
-    assert rel_err(a[tuple(np.array(iu).T)], ref) < TOL
+    assert tuple(seqs) == sp.dense_set("col")[0]
+    _twin_check(a[tuple(np.array(iu).T)], seqs, kern, iu, sp.dense_ref("col", 0.8, 0))
     assert a[n - 4, n - 4] == 1.0 and np.all(a[n - 4, :] == 1.0)  # the empty sequence: K = 1
 
 
@@ -138,11 +153,9 @@ def test_stem4d_params_and_predict(gpu_ctx):
     x = np.array([0, 1, 4, 2], np.int32)
     y = np.array([3, 1, 0, 4], np.int32)
     got = gpu_ctx.pairs(ds, kern, x, y)
-    ref = _oracle(seqs, kern, list(zip(x, y)))
-    assert rel_err(got, ref) < TOL
+    _twin_check(got, seqs, kern, list(zip(x, y)))
     row = gpu_ctx.test_row(ds, 1, ds, kern)
-    ref = _oracle(seqs, kern, [(i, 1) for i in range(5)])
-    assert rel_err(row, ref) < TOL
+    _twin_check(row, seqs, kern, [(i, 1) for i in range(5)])
 
 
 @pytest.mark.gpu
@@ -159,11 +172,7 @@ def test_stem4d_resident_tables_two_datasets(gpu_ctx):
     for kern in [ska.StemKernel4D(bp_model=1, bp_bound=0.5), ska.StemKernel4D(),
                  ska.StemKernel4D(bp_model=2, bp_bound=0.5, loop=5)]:
         got, _ = gpu_ctx.test_matrix(dte, dtr, kern)
-        p = kern.params
-        ref = np.array([[po.stem4d(a.lower(), ska.fold(a), b.lower(), ska.fold(b), p.gap, p.stack,
-                                   p.subst, p.bp_bound, p.bp_model, p.loop, p.len_band,
-                                   p.ali_bound, p.ali_zerop_fixed) for b in tr] for a in te])
-        assert rel_err(got, ref) < TOL
+        _twin_check(got, te + tr, kern, [(a, len(te) + b) for a in range(len(te)) for b in range(len(tr))])
 
 
 @pytest.mark.gpu
@@ -181,8 +190,7 @@ def test_stem4d_col_cpl8_matches_oracle(gpu_ctx):
     y = np.array([3, 3, 4, 4, 3], np.int32)
     got = gpu_ctx.pairs(ds, kern, x, y)
     assert gpu_ctx.last_classes()["stem4d_col"] == [8]
-    ref = _oracle(seqs, kern, list(zip(x, y)))
-    assert rel_err(got, ref) < TOL
+    _twin_check(got, seqs, kern, list(zip(x, y)))
 
 
 @pytest.mark.gpu
@@ -199,8 +207,7 @@ def test_stem4d_short_y_limits(gpu_ctx):
     x = np.array([p[0] for p in pairs], np.int32)
     y = np.array([p[1] for p in pairs], np.int32)
     got = gpu_ctx.pairs(ds, kern, x, y)
-    ref = _oracle(seqs, kern, pairs)
-    assert rel_err(got, ref) < TOL
+    _twin_check(got, seqs, kern, pairs)
 
 
 def test_oracle_band_wide_equals_full_dp():
@@ -225,13 +232,12 @@ def test_stem4d_banded_matches_oracle(gpu_ctx, band):
     n = len(seqs)
     iu = list(zip(*np.triu_indices(n)))
     got = gpu_ctx.gram(ds, kern)
-    ref = _oracle(seqs, kern, iu)
-    assert rel_err(got[tuple(np.array(iu).T)], ref) < TOL
+    _twin_check(got[tuple(np.array(iu).T)], seqs, kern, iu)
     # asymmetric lengths in both orders
     x = np.array([3, 0, 5, 6], np.int32)
     y = np.array([0, 3, 1, 2], np.int32)
     got = gpu_ctx.pairs(ds, kern, x, y)
-    assert rel_err(got, _oracle(seqs, kern, list(zip(x, y)))) < TOL
+    _twin_check(got, seqs, kern, list(zip(x, y)))
 
 
 @pytest.mark.gpu
